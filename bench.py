@@ -25,10 +25,9 @@ import sys
 import time
 
 # The step keeps two streams busy (student / teacher pass) next to torch's current stream, the gradient-sum stream, the
-# all-reduce stream and RCCL's own.  HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) round-robin, and two
-# streams that share a queue run one after the other: measured with the 1-rank RCCL path, 30.6 ms/step with 4 queues vs
-# 25.9 with 8 (without RCCL: 25.9 either way).  Must be set before the HIP runtime initialises, i.e. before `import torch`.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# all-reduce stream and RCCL's own.  HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues round-robin, and two streams that
+# share a queue run one after the other.  The queue count is the environment's to choose (on a shared card every process's
+# queues come out of one fixed pool of slots), so this script does not raise it; the JSON line records the value it ran with.
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "dynamic-tuning_amd")):
@@ -50,6 +49,7 @@ PEAK = {"bf16": 2500.0, "fp16": 2500.0, "fp32": 157.3,   # TFLOP/s dense MFMA, M
         "fp16f8": 2500.0 / 1.5}  # forward: one f16 product + two fp8 products at twice the rate = two f16-equivalents; backward one  # the same product counts; the backward runs on 16-bit operands with the fp16 mode's kernels
 TRAFFIC_JSON = os.path.join("round6", "gemm_traffic.json")
 SUSTAINED_MFMA_TFLOPS = 1670.0   # measured, see roofline.sustained_mfma_measured
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: at most this much in all
 
 
 class Cfg(dict):
@@ -161,6 +161,9 @@ def main():
     ap.add_argument("--video-frames", type=int, default=0,
                     help="T > 1: BASELINE.json configs[4] shape instead of the headline one -- the video model, "
                          "--batch frames per GPU = batch/T clips of T frames (train_video.sh: 16 clips x 8 frames, 400 classes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step returned (loss components, trainable parameters "
+                         "after the update) as DIR/<name>.npy, float32, at most 64 MB in all; the inputs depend only on the arguments")
     args = ap.parse_args()
     if args.precision is None:
         # headline mode: IEEE-half operands (the reference's own GPU dtype: it trains under fp16 autocast, engine_finetune.py:47) --
@@ -211,7 +214,8 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
     assert world == args.gpus, "launch with torch.distributed.run --nproc-per-node %d" % args.gpus
 
-    head = measure(args, args.precision, args.mode, args.steps, args.warmup, device, world, rank, host_batches=args.host_batches)
+    head = measure(args, args.precision, args.mode, args.steps, args.warmup, device, world, rank, host_batches=args.host_batches,
+                   dump_dir=args.dump_outputs)
     side_errors = {}
 
     def side(name, *a, **kw):
@@ -419,9 +423,35 @@ def host_fed(args, model, opt, steps, warmup, device, world, resident_ms):
                     "`copy_on_compute_stream` = the reference's placement of the copy (DYT_PREFETCH=0)"}
 
 
-def measure(args, precision, mode, steps, warmup, device, world, rank, host_batches=0):
+def dump_outputs(dump_dir, model, losses):
+    """What the last timed step hands its caller, as float32 .npy files: `losses.npy` (train_step's return value, the 8 loss
+    components) and `param.<name>.npy` for every trainable parameter after that step's AdamW update.  Over DUMP_MAX_BYTES in
+    all (128 bytes of .npy header counted per file), every array of more than 4096 elements is cut to a fixed, seeded sample of
+    its flattened elements (same indices for the same arguments)."""
+    import numpy as np
+    arrays = {"losses": losses}
+    arrays.update(("param." + n, p) for n, p in model.named_parameters() if p.requires_grad)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    budget = DUMP_MAX_BYTES - 128 * len(arrays)
+    big = [k for k, a in arrays.items() if a.size > 4096]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        small = total - sum(arrays[k].nbytes for k in big)
+        frac = (budget - small) / (total - small)
+        rng = np.random.default_rng(0)
+        for k in big:
+            a = arrays[k].reshape(-1)
+            arrays[k] = a[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+    os.makedirs(dump_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dump_dir, k + ".npy"), a)
+    log("dumped %d arrays (%.1f MB) of the last timed step to %s" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6, dump_dir))
+
+
+def measure(args, precision, mode, steps, warmup, device, world, rank, host_batches=0, dump_dir=None):
     """Build the model in one arithmetic / training mode, calibrate the keep ratio, time `steps` fused steps (barrier +
-    synchronize on both sides, max over ranks) and take the dominant-kernel roofline of one extra event-profiled step."""
+    synchronize on both sides, max over ranks) and take the dominant-kernel roofline of one extra event-profiled step.
+    dump_dir: write what the last timed step returned (dump_outputs)."""
     from engine_finetune import FusedAdamW, train_step
     margs = argparse.Namespace(**vars(args))
     margs.precision, margs.mode = precision, mode
@@ -446,8 +476,8 @@ def measure(args, precision, mode, steps, warmup, device, world, rank, host_batc
     acc = torch.zeros(8, device=device)
 
     def one_step(i, update=True):
-        train_step(model, x, y, opt, losses_out=losses, seed=1000 + i, target_ratio=args.keep, token_minimal=0.0,
-                   token_minimal_weight=0.0, graph=use_graph, update=update)
+        return train_step(model, x, y, opt, losses_out=losses, seed=1000 + i, target_ratio=args.keep, token_minimal=0.0,
+                          token_minimal_weight=0.0, graph=use_graph, update=update)
 
     for i in range(warmup):
         one_step(i)
@@ -457,12 +487,14 @@ def measure(args, precision, mode, steps, warmup, device, world, rank, host_batc
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        one_step(warmup + i)
+        last = one_step(warmup + i)
         acc += losses
     if dist.is_initialized():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:   # before the extra steps below move the parameters again
+        dump_outputs(dump_dir, model, last)
     # host cost of a step: enqueue two steps into EMPTY queues (inside the timed loop the host runs ahead of the GPU until the
     # hardware queues are full and then only measures back-pressure -- round 1's "13.6 ms" was that)
     th0 = time.perf_counter()

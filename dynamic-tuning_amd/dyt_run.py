@@ -17,9 +17,6 @@ import os
 import runpy
 import sys
 
-# before the HIP runtime starts: the step's pass streams + gradient-sum + all-reduce + RCCL streams need more than four hardware queues
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 

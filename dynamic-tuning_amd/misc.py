@@ -92,9 +92,6 @@ def init_distributed_mode(args):
         args.distributed = False
         return
     args.distributed = True
-    # one process per GPU; the step's two pass streams, the gradient-sum stream, the all-reduce stream and RCCL's own need more than
-    # HIP's default four hardware queues -- effective when the HIP runtime has not started yet
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")
     torch.cuda.set_device(args.gpu)
     args.dist_backend = "nccl"
     print("| distributed init (rank %d): %s, gpu %d" % (args.rank, getattr(args, "dist_url", "env://"), args.gpu), flush=True)

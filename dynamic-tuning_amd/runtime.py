@@ -315,7 +315,7 @@ class DyTEngine:
 
     def streams_concurrent(self, a, b, spin_cycles=400_000, repeats=3):
         """True when work queued on streams `a` and `b` really runs at the same time.  HIP multiplexes a process's streams onto
-        GPU_MAX_HW_QUEUES hardware queues (default 4; _lib.py / bench.py ask for 8 when they are imported before the runtime starts) and two
+        GPU_MAX_HW_QUEUES hardware queues (the launching environment's choice) and two
         streams on one queue run one after the other -- a DP rank's all-reduce stream sharing the step's queue costs 30.6 instead of 25.9
         ms per step.  Measured, not assumed: one ~0.2 ms spin kernel on each stream; together they take ~1x (separate
         queues) or ~2x (same queue) the time of one.  Best of `repeats` trials, so that a busy or shared GPU (another process's kernel
@@ -349,8 +349,8 @@ class DyTEngine:
 
     def comm_stream(self):
         """Side stream of the early gradient all-reduce: one that is VERIFIED to run beside the step's stream (up to eight candidates; streams
-        map to hardware queues in creation order).  If none does -- a launcher imported torch before GPU_MAX_HW_QUEUES could be raised and
-        the queues are exhausted -- a warning names the cause; DYT_STRICT=1 turns it into an error."""
+        map to hardware queues in creation order).  If none does -- the process has fewer hardware queues than streams and the queues are
+        exhausted -- a warning names the cause; DYT_STRICT=1 turns it into an error."""
         if self._comm_stream is None:
             import os
             import warnings
@@ -364,8 +364,8 @@ class DyTEngine:
                     break
             if self._comm_stream is None:
                 msg = ("the gradient all-reduce stream shares a hardware queue with the step's stream on %s (GPU_MAX_HW_QUEUES=%s): the "
-                       "all-reduce will run after the backward pass instead of under it; export GPU_MAX_HW_QUEUES=8 before the HIP runtime "
-                       "starts" % (self.device, os.environ.get("GPU_MAX_HW_QUEUES", "unset (4)")))
+                       "all-reduce will run after the backward pass instead of under it; the process needs more hardware queues, set before the "
+                       "HIP runtime starts" % (self.device, os.environ.get("GPU_MAX_HW_QUEUES", "unset (4)")))
                 if os.environ.get("DYT_STRICT", "0") == "1":
                     raise DyTError(msg)
                 warnings.warn(msg)

@@ -145,7 +145,7 @@ int dyt_ctx_bytes(const dyt_ctx* ctx, int64_t* bytes);
  *                           teacher pass on two streams (fork/join with events on the caller's stream).  2: additionally
  *                           the adapter branch of every block on its own stream, 3: only that -- both measured SLOWER
  *                           than 1 whenever the branch streams really get their own hardware queues (26.1 vs 31.5 /
- *                           30.0 ms per step at B=128 with GPU_MAX_HW_QUEUES=8; the serial step is 29.5 ms), kept for
+ *                           30.0 ms per step at B=128 with a hardware queue per stream; the serial step is 29.5 ms), kept for
  *                           measurement only.  4: the two FORWARD passes overlap, the teacher's backward starts after the
  *                           student's -- like 0 a bit-reproducible schedule, 29.0 instead of 26.1 ms
  *   DYT_OPT_CLS_TAIL        last block: evaluate MLP + adapter (forward and backward) for the cls rows
