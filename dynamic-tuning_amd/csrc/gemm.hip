@@ -331,6 +331,7 @@ struct EpiGeluBwd {
 
 struct EpiStoreF32 {
     float* out; int ld; int accumulate; float alpha;   // out (+)= alpha * acc
+    const float* dscale = nullptr;                     // device word alpha is multiplied by (GemmArgs::out_dscale)
     typedef NoCtx Col; typedef Raw4<float> Pre;
     __device__ __forceinline__ Col col_init(int) const { return {}; }
     __device__ __forceinline__ Pre pre(int row, int col) const {
@@ -340,17 +341,24 @@ struct EpiStoreF32 {
     __device__ __forceinline__ void apply(int row, int col, const float (&a)[4], const Col&, const Pre& p) const {
         float r[4];
         p.get(r);
-        store4(out + (size_t)row * ld + col, r[0] + alpha * a[0], r[1] + alpha * a[1], r[2] + alpha * a[2], r[3] + alpha * a[3]);
+        const float al = dscale ? alpha * *dscale : alpha;
+        store4(out + (size_t)row * ld + col, r[0] + al * a[0], r[1] + al * a[1], r[2] + al * a[2], r[3] + al * a[3]);
     }
 };
 
 template <class AT>
 struct EpiStoreAT {
     AT* out; int ld;
+    const float* dscale = nullptr;   // device word the result is multiplied by (GemmArgs::out_dscale)
     typedef NoCtx Col; typedef NoCtx Pre;
     __device__ __forceinline__ Col col_init(int) const { return {}; }
     __device__ __forceinline__ Pre pre(int, int) const { return {}; }
     __device__ __forceinline__ void apply(int row, int col, const float (&a)[4], const Col&, const Pre&) const {
+        if (dscale) {   // (uniform branch)
+            const float f = *dscale;
+            store4(out + (size_t)row * ld + col, a[0] * f, a[1] * f, a[2] * f, a[3] * f);
+            return;
+        }
         store4(out + (size_t)row * ld + col, a[0], a[1], a[2], a[3]);
     }
 };
@@ -1429,8 +1437,8 @@ static int dispatch(EpiKind kind, const GemmArgs& a, hipStream_t s) {
         case EPI_GELU_BWD:
             if (a.row_map) return run<AT, SPLIT>(a, EpiGeluBwd<AT, true>{(const AT*)a.aux_at, (AT*)a.out_at, a.N, a.row_map, (bf16*)a.out3, a.out3_scale, a.out3_hi_only}, s);
             return run<AT, SPLIT>(a, EpiGeluBwd<AT, false>{(const AT*)a.aux_at, (AT*)a.out_at, a.N, nullptr, (bf16*)a.out3, a.out3_scale, a.out3_hi_only}, s);
-        case EPI_STORE_F32: return run<AT, SPLIT>(a, EpiStoreF32{a.out_f32, a.N, a.accumulate, a.scale}, s);
-        case EPI_STORE_AT: return run<AT, SPLIT>(a, EpiStoreAT<AT>{(AT*)a.out_at, a.N}, s);
+        case EPI_STORE_F32: return run<AT, SPLIT>(a, EpiStoreF32{a.out_f32, a.N, a.accumulate, a.scale, a.out_dscale}, s);
+        case EPI_STORE_AT: return run<AT, SPLIT>(a, EpiStoreAT<AT>{(AT*)a.out_at, a.N, a.out_dscale}, s);
         case EPI_AD_DOWN:
             if constexpr (!SPLIT && sizeof(AT) == 4) {
                 if (a.save16) return run<AT, SPLIT>(a, EpiAdDown<AT, bf16>{a.bias, (AT*)a.out_at, a.keep, a.r, a.inv_keep, a.drop_p, a.seed, a.subseq, a.row_map, a.seed_dev, (bf16*)a.out_at2, a.scale, (bf16*)a.out3, a.out3_scale}, s);

@@ -91,6 +91,9 @@ struct GemmArgs {
     const float* row_scale = nullptr;
     // skinny K >= 1024 GEMMs (the cls-only last block): workspace for the split-K form (gemm_skinny.h), [slices][M][N] fp32; null = tile kernels
     float* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;
+    // STORE_F32 / STORE_AT: the result is also multiplied by *out_dscale (a device word; null = 1).  The adapter's down_proj dgrad takes
+    // the power of two its operand ddz carries (adapter_lift_exp) back out with it, without a host sync
+    const float* out_dscale = nullptr;
     double flops() const { return 2.0 * M * (double)N * K; }
 };
 
@@ -294,6 +297,7 @@ struct TokBwdArgs {
     const void* cat_ddz = nullptr;    // [M, 64] AT
     const float* cat_bup = nullptr;   // unused (kept for ABI stability of the struct)
     float cat_scale = 0.f, cat_ddz_scale = 0.f;   // s ; 1 / (inv_keep * gs)
+    const float* cat_ddz_dscale = nullptr;          // device word: cat_ddz_scale is multiplied by it (ddz's 2^-e, adapter_lift_exp; null = 1)
     void* du3 = nullptr;           // fp32 split form: + du * du3_scale as the [M][3*768] 16-bit hi / hi / lo operand of the proj dgrad
     float du3_scale = 1.0f; bool du3_hi_only = false;   // hi_only: without the lo half (one-part proj dgrad)
     // stochastic depth: the MLP branch of image b was multiplied by branch_scale[b] in the forward pass (GemmArgs::row_scale of FC2), so
@@ -327,19 +331,32 @@ struct WgradArgs {
     // fp32 mode only: the products on the 16-bit matrix cores from fp32 inputs converted as they are loaded (one-part gradient
     // products of "fp16x3f"); X / Y are multiplied by x_scale / y_scale (powers of two) first, the outputs divided again
     bool half_products = false; float x_scale = 1.f, y_scale = 1.f;
+    const float* alpha_dev = nullptr;   // device word all three alphas are multiplied by (null = 1): ddz's 2^-e (adapter_lift_exp)
 };
 // Reductions of per-chunk partials deferred to ONE batched launch (the backward pass queues the adapter weight-gradient and the
 // gate-gradient reductions of several blocks -- each with its own partial buffer -- and flushes them where the gradients have to
 // be final: 36 latency-bound launches per pass become 4).  Fixed summation order per output, as the immediate form.
 struct WgReduceDesc {
     const float* partial; float* out_w; int sc, sj; float alpha; float* out_xsum; float alpha_x; float* out_ysum; float alpha_y;
-    int nchunks;
+    int nchunks; const float* alpha_dev;
 };
 struct ReduceQueue {
     static constexpr int MAX_WG = 32, MAX_TOK = 16;
     WgReduceDesc wg[MAX_WG]; int n_wg = 0; int r = 0;
     const float* tok_partial[MAX_TOK]; float* tok_out[MAX_TOK]; int tok_nparts[MAX_TOK]; int n_tok = 0;
 };
+// Power of two 2^e (e >= 0) a 16-bit operand whose largest magnitude is amax is lifted by before it is stored.  A zero-initialised up_proj
+// (reference models/dynamic_adapter.py:112-117) grows through 1e-8 .. 1e-4 over the first warm-up steps: below IEEE half's normal range,
+// where the up_proj dgrad's product ddz = g W_up would go subnormal or flush.  e = 0 while amax >= 2^-7 (every weight magnitude of the
+// parity tests and the benchmark: results there are bit-identical to an unscaled operand); below, e brings amax into [2^-4, 2^-3), the
+// range of an N(0, 0.02) matrix.  Capped so that 2^-e stays a normal fp32.
+__host__ __device__ inline int adapter_lift_exp(float amax) {
+    if (!(amax > 0.f) || amax >= 0.0078125f) return 0;   // 0 / NaN: nothing to lift
+    int ex;
+    frexpf(amax, &ex);                                    // amax in [2^(ex-1), 2^ex)
+    const int e = -3 - ex;
+    return e < 120 ? e : 120;
+}
 int launch_wgrad(int precision, const WgradArgs& a, hipStream_t s);
 // two products with the same M and r (separate `partial` buffers) as one launch + one reduce launch (defer: queued instead)
 int launch_wgrad(int precision, const WgradArgs* a, int n, hipStream_t s, ReduceQueue* defer = nullptr);

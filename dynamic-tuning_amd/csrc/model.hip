@@ -44,7 +44,8 @@ template <class AT>
 __global__ void prep_adapters_kernel(const float* __restrict__ flat, int64_t layer_stride, int64_t off_dw, int64_t off_db,
                                      int64_t off_uw, int r, AT* __restrict__ down_w, AT* __restrict__ down_wT,
                                      AT* __restrict__ up_w, AT* __restrict__ up_wT, float* __restrict__ down_b,
-                                     AT* __restrict__ up_ws, float scale, int64_t off_sc, int64_t off_ub, float* __restrict__ up_bp, float bias_scale) {
+                                     AT* __restrict__ up_ws, float scale, int64_t off_sc, int64_t off_ub, float* __restrict__ up_bp, float bias_scale,
+                                     const float* __restrict__ up_t_lift) {
     // off_sc >= 0 ("learnable_scalar", DYT_OPT_LEARNABLE_SCALE): the up-projection copies and up_bp [depth][768] carry the block's trainable
     // scale s = flat[off_sc] (W' = s W_up, b' = s b_up), and every kernel downstream runs with scale 1
     const int l = blockIdx.y;
@@ -58,7 +59,7 @@ __global__ void prep_adapters_kernel(const float* __restrict__ flat, int64_t lay
         const float dw = j < r ? base[off_dw + (int64_t)j * D + c] : 0.f;   // down_proj.weight [r,768]
         const float uw = j < r ? ls * base[off_uw + (int64_t)c * r + j] : 0.f;   // up_proj.weight [768,r]
         down_w[(size_t)l * SZ + idx] = from_f32<AT>(dw);
-        up_wT[(size_t)l * SZ + idx] = from_f32<AT>(uw);
+        up_wT[(size_t)l * SZ + idx] = from_f32<AT>(up_t_lift ? uw * up_t_lift[l] : uw);
     }
     {   // idx -> (c, j) of [768,RP]
         const int c = idx / RP, j = idx - c * RP;
@@ -70,6 +71,30 @@ __global__ void prep_adapters_kernel(const float* __restrict__ flat, int64_t lay
     }
     if (idx < RP) down_b[l * RP + idx] = idx < r ? base[off_db + idx] : 0.f;
     if (up_bp && idx < D) up_bp[l * D + idx] = bias_scale * ls * base[off_ub + idx];   // bias_scale: the adapter's LayerNorm "out" form takes s b_up here
+}
+
+// up_t_lift of prep_adapters_kernel: lift[l] = 2^e, lift[depth + l] = 2^-e with e = adapter_lift_exp(max |s W_up|) of block l (s: the learnable
+// scale, else 1).  The 16-bit up_proj dgrad operand up_wT carries 2^e, so its product ddz carries gs 2^e, and every consumer of ddz takes 2^-e
+// back out (WgradArgs::alpha_dev, GemmArgs::out_dscale, TokBwdArgs::cat_ddz_dscale).  One workgroup per block, on the device: no host sync.
+__global__ __launch_bounds__(256) void adapter_lift_kernel(const float* __restrict__ flat, int64_t layer_stride, int64_t off_uw, int64_t off_sc,
+                                                           int r, int depth, float* __restrict__ lift) {
+    __shared__ float red[256];
+    const int l = blockIdx.x, tid = threadIdx.x;
+    const float* base = flat + (int64_t)l * layer_stride;
+    const float ls = off_sc >= 0 ? base[off_sc] : 1.0f;
+    float m = 0.f;
+    for (int i = tid; i < D * r; i += 256) m = fmaxf(m, fabsf(ls * base[off_uw + i]));
+    red[tid] = m;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int e = adapter_lift_exp(red[0]);
+        lift[l] = ldexpf(1.0f, e);
+        lift[depth + l] = ldexpf(1.0f, -e);
+    }
 }
 
 // "learnable_scalar": the backward has left G' = dL/dW', gb' = dL/db' of the PRIMED up-projection (W' = s W_up, b' = s b_up) of every block
@@ -296,6 +321,7 @@ struct dyt_ctx {
     void* ad_up_ws = nullptr;   // "out": [depth][768][RP] adapter_scale * up_proj.weight in the forward's operand type (the LayerNorm input is s (d_act W^T + b))
     bool pass_ran = false;       // a forward pass has run in this context: DYT_OPT_LEARNABLE_SCALE may no longer change
     float* ad_up_bp = nullptr;   // [depth][768] s * up_proj.bias (prep_adapters_kernel)
+    float* ad_lift = nullptr;    // [2][depth] 2^e / 2^-e of the 16-bit up_proj dgrad operand (adapter_lift_kernel)
     float drop_path_rate = 0.f;  // timm DropPath rate of the LAST block (block l: rate * l / (depth - 1)); training forward passes only
     int count_flops_tokens = 0;  // > 0: Block.forward_count_flops -- MLP on the first n tokens of every image
     // profiling
@@ -357,6 +383,7 @@ static void layout(dyt_ctx* c, bool dry) {
     c->ad_up_w = carve_at(c, depth * RP * D, dry);
     c->ad_up_wT = carve_at(c, depth * RP * D, dry);
     c->ad_down_b = carve<float>(c, depth * RP, dry);
+    c->ad_lift = carve<float>(c, 2 * depth, dry);
     c->slots.resize(cf.slots);
     for (int s = 0; s < cf.slots; ++s) {
         Slot& S = c->slots[s];
@@ -1036,15 +1063,19 @@ static int prep_adapters(dyt_ctx* c, const float* trainable, hipStream_t s) {
     const bool out_ln = c->ad_ln == 2;
     float* up_bp = (c->learn_scale || out_ln) ? c->ad_up_bp : nullptr;
     const float ws_scale = out_ln ? c->cfg.adapter_scale : 0.f, b_scale = out_ln ? c->cfg.adapter_scale : 1.0f;
+    if (c->prec != 0 || c->bwd16)   // the 16-bit up_proj dgrad operand's power of two (read by prep_adapters_kernel<bf16> and the backward)
+        hipLaunchKernelGGL(adapter_lift_kernel, dim3(c->cfg.depth), dim3(256), 0, s, trainable, c->layer_stride, c->off_uw, sc_off,
+                           c->cfg.ffn_num, c->cfg.depth, c->ad_lift);
     if (c->prec == 0) {
         hipLaunchKernelGGL(prep_adapters_kernel<float>, grid, dim3(256), 0, s, trainable, c->layer_stride, c->off_dw, c->off_db,
                            c->off_uw, c->cfg.ffn_num, (float*)c->ad_down_w, (float*)c->ad_down_wT, (float*)c->ad_up_w,
-                           (float*)c->ad_up_wT, c->ad_down_b, out_ln ? (float*)c->ad_up_ws : (float*)nullptr, ws_scale, sc_off, c->off_ub, up_bp, b_scale);
+                           (float*)c->ad_up_wT, c->ad_down_b, out_ln ? (float*)c->ad_up_ws : (float*)nullptr, ws_scale, sc_off, c->off_ub, up_bp, b_scale,
+                           (const float*)nullptr);
         if (c->bwd16) {   // + the 16-bit transposes the 16-bit backward's adapter dgrads multiply by
             bf16* scr = (bf16*)c->ad_scratch16;
             hipLaunchKernelGGL(prep_adapters_kernel<bf16>, grid, dim3(256), 0, s, trainable, c->layer_stride, c->off_dw, c->off_db,
                                c->off_uw, c->cfg.ffn_num, scr, (bf16*)c->ad_down_wT16, scr + (size_t)c->cfg.depth * RP * D,
-                               (bf16*)c->ad_up_wT16, c->ad_down_b, (bf16*)nullptr, 0.f, sc_off, c->off_ub, up_bp, b_scale);
+                               (bf16*)c->ad_up_wT16, c->ad_down_b, (bf16*)nullptr, 0.f, sc_off, c->off_ub, up_bp, b_scale, (const float*)c->ad_lift);
             if (c->ad_up_w3) {   // [hi | lo] image of the fp32 up-projection copies just written (all blocks: depth * 768 rows of 64)
                 int rc = launch_split3_w((const float*)c->ad_up_w, c->ad_up_w3, c->cfg.depth * D, RP, s);
                 if (rc) return rc;
@@ -1053,7 +1084,8 @@ static int prep_adapters(dyt_ctx* c, const float* trainable, hipStream_t s) {
     } else
         hipLaunchKernelGGL(prep_adapters_kernel<bf16>, grid, dim3(256), 0, s, trainable, c->layer_stride, c->off_dw, c->off_db,
                            c->off_uw, c->cfg.ffn_num, (bf16*)c->ad_down_w, (bf16*)c->ad_down_wT, (bf16*)c->ad_up_w,
-                           (bf16*)c->ad_up_wT, c->ad_down_b, out_ln ? (bf16*)c->ad_up_ws : (bf16*)nullptr, ws_scale, sc_off, c->off_ub, up_bp, b_scale);
+                           (bf16*)c->ad_up_wT, c->ad_down_b, out_ln ? (bf16*)c->ad_up_ws : (bf16*)nullptr, ws_scale, sc_off, c->off_ub, up_bp, b_scale,
+                           (const float*)c->ad_lift);
     DYT_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1663,6 +1695,8 @@ static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const flo
                    *qkv_wT = b16 ? W.qkv_wT16 : W.qkv_wT, *qkv_wTp = b16 ? W.qkv_wTp16 : W.qkv_wTp;
         void* ad_up_wT = b16 ? c->ad_up_wT16 : c->ad_up_wT; void* ad_down_wT = b16 ? c->ad_down_wT16 : c->ad_down_wT;
         void* Tdad = b16 ? T.dad16 : T.dad;
+        // 16-bit backward: ad_up_wT carries 2^e (adapter_lift_kernel), so ddz carries gs 2^e; its consumers multiply by this 2^-e
+        const float* ddz_unlift = P != 0 ? c->ad_lift + depth + l : nullptr;
 
         const bool tail = cls_tail && l == depth - 1;  // incoming gradient lives at the cls rows only (S.gcls)
         const int Mr = tail ? B : M;
@@ -1712,6 +1746,7 @@ static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const flo
             b.out_w = gbase + c->off_dw; b.sc = 1; b.sj = D; b.alpha = inv_gs;      // down_proj.weight [r, 768]  (Y = ddz carries gs)
             b.out_xsum = nullptr; b.alpha_x = 0.f;
             b.out_ysum = gbase + c->off_db; b.alpha_y = inv_gs;                     // down_proj.bias
+            b.alpha_dev = ddz_unlift;
             if (split16 && c->split_bwd_parts == 1 && c->split_wgrad16) {   // "fp16x3f": gradient products one-part here too
                 a.half_products = b.half_products = true;
                 a.x_scale = c->split_gs;   // X = g (gradient-sized), Y = d_act
@@ -1747,7 +1782,7 @@ static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const flo
         if (ad_in) {
             // "in": ddz W_down is the gradient w.r.t. LN_a(u): the LayerNorm's parameter gradients from it (block 0 included), then its input gradient --
             // 16-bit backward: a 16-bit operand tok_bwd adds (T.dup); fp32 backward: accumulated into g
-            GemmArgs a; a.A = T.ddz; a.W = at_offb(ad_down_wT, (size_t)l * RP * D); a.M = Mr; a.N = D; a.K = RP;
+            GemmArgs a; a.A = T.ddz; a.W = at_offb(ad_down_wT, (size_t)l * RP * D); a.M = Mr; a.N = D; a.K = RP; a.out_dscale = ddz_unlift;
             if (P != 0) { a.out_at = Tdad; ISO(16, RUN_GEMM(EPI_STORE_AT, a);); }
             else { a.out_f32 = T.dup; a.accumulate = 0; a.scale = 1.0f; ISO(16, RUN_GEMM(EPI_STORE_F32, a);); }
             const void* dln = P != 0 ? (const void*)Tdad : (const void*)T.dup;
@@ -1757,7 +1792,7 @@ static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const flo
                 else RUN(2, 0, launch_ln_bwd(P, dln, L.u, L.st_a, base + c->off_alw, gin, gin, Mr, nullptr, nullptr, nullptr, nullptr, gs, s));
             }
         } else if (!first) {
-            GemmArgs a; a.A = T.ddz; a.W = at_offb(ad_down_wT, (size_t)l * RP * D); a.M = Mr; a.N = D; a.K = RP;
+            GemmArgs a; a.A = T.ddz; a.W = at_offb(ad_down_wT, (size_t)l * RP * D); a.M = Mr; a.N = D; a.K = RP; a.out_dscale = ddz_unlift;
             if (dad_at) { a.out_at = Tdad; POISON(4, Tdad, (size_t)Mr * D * atb); ISO(16, RUN_GEMM(EPI_STORE_AT, a);); }
             else { a.out_f32 = gin; a.accumulate = 1; a.scale = inv_gs; ISO(16, RUN_GEMM(EPI_STORE_F32, a);); }
             if (dad_at) CK("ad_dgrad_down dad", Tdad, (size_t)Mr * D * atb);   // g <- g + ddz Wdown
@@ -1776,7 +1811,7 @@ static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const flo
             a.gs = gs; a.inv_gs = inv_gs;
             if (L.h_has_adapter && student && !tail) {
                 a.cat_dact = Ldact; a.cat_ddz = T.ddz; a.cat_bup = base + c->off_ub;
-                a.cat_scale = scale; a.cat_ddz_scale = 1.0f / (inv_keep * gs);
+                a.cat_scale = scale; a.cat_ddz_scale = 1.0f / (inv_keep * gs); a.cat_ddz_dscale = ddz_unlift;
             }
             a.dtoken_select = dtoken_select ? dtoken_select + (size_t)l * NP : nullptr;
             a.dtoken_logits = dtoken_logits ? dtoken_logits + (size_t)l * NP : nullptr;
@@ -2267,6 +2302,24 @@ __global__ __launch_bounds__(256) void mask_to_keep_kernel(const float* __restri
     if (keep) keep_local[(size_t)b * NT + off + __popcll(bal & ((1ull << lane) - 1ull))] = tid;
     if (tid == 0) counts[b] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
 }
+// dyt_adapter_bwd's lifts: *out = max |x| over n floats (as the bit pattern of a non-negative float, which orders like the value;
+// *out zeroed by the caller), and dst = f src
+__global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, int64_t n, unsigned* __restrict__ out) {
+    __shared__ float red[256];
+    float m = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(out, __float_as_uint(red[0]));
+}
+__global__ void scale_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n, float f) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[i] * f;
+}
 }  // namespace dyt
 
 struct AdapterOps {   // AT copies of one adapter's weights in the layouts the GEMMs want (see prep_adapters_kernel)
@@ -2342,6 +2395,37 @@ extern "C" int dyt_adapter_bwd(const float* x, const float* down_w, const float*
     const int P = precision;
     const size_t at = at_size(P);
     Scratch sc;
+    // 16-bit operands: up_w and dout are lifted by powers of two 2^ew, 2^ed (adapter_lift_exp of their absmax) before they are converted --
+    // a zero-initialised up_proj and gradient-sized dout sit below IEEE half's normal range -- and ddz carries 2^(ed + ew) out to its consumers
+    int ew = 0, ed = 0;
+    if (P != 0) {
+        unsigned* am = (unsigned*)sc.get(2 * sizeof(unsigned));
+        if (!am) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+        DYT_HIP_CHECK(hipMemsetAsync(am, 0, 2 * sizeof(unsigned), s));
+        hipLaunchKernelGGL(absmax_kernel, dim3(64), dim3(256), 0, s, up_w, (int64_t)D * r, am);
+        hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, s, dout, (int64_t)M * D, am + 1);
+        unsigned h[2];
+        DYT_HIP_CHECK(hipMemcpyAsync(h, am, sizeof(h), hipMemcpyDeviceToHost, s));
+        DYT_HIP_CHECK(hipStreamSynchronize(s));
+        float fa[2];
+        memcpy(fa, h, sizeof(fa));
+        ew = adapter_lift_exp(fa[0]);
+        ed = adapter_lift_exp(fa[1]);
+        if (ew > 0) {
+            float* uw = (float*)sc.get((size_t)D * r * sizeof(float));
+            if (!uw) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+            hipLaunchKernelGGL(scale_copy_kernel, dim3((D * r + 255) / 256), dim3(256), 0, s, up_w, uw, (int64_t)D * r, ldexpf(1.0f, ew));
+            up_w = uw;   // (only its transpose up_wT is read below)
+        }
+        if (ed > 0) {
+            float* dl = (float*)sc.get((size_t)M * D * sizeof(float));
+            if (!dl) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+            hipLaunchKernelGGL(scale_copy_kernel, dim3((unsigned)(((int64_t)M * D + 255) / 256)), dim3(256), 0, s, dout, dl, (int64_t)M * D, ldexpf(1.0f, ed));
+            dout = dl;
+        }
+        DYT_HIP_CHECK(hipGetLastError());
+    }
+    const float inv_d = ldexpf(1.0f, -ed), inv_dw = ldexpf(1.0f, -(ed + ew));   // 1 at precision 0
     AdapterOps o;
     int rc = adapter_prepare(sc, P, x, down_w, down_b, up_w, M, r, &o, s);
     if (rc) return rc;
@@ -2360,12 +2444,12 @@ extern "C" int dyt_adapter_bwd(const float* x, const float* down_w, const float*
     }
     WgradArgs w[2];
     w[0].X = g_at; w[0].Y = o.d_act; w[0].M = M; w[0].r = r; w[0].partial = p1; w[0].out_w = d_up_w; w[0].sc = r; w[0].sj = 1;
-    w[0].alpha = scale; w[0].out_xsum = d_up_b; w[0].alpha_x = scale;
+    w[0].alpha = scale * inv_d; w[0].out_xsum = d_up_b; w[0].alpha_x = scale * inv_d;   // X = g_at carries 2^ed
     w[1].X = o.x_at; w[1].Y = ddz; w[1].M = M; w[1].r = r; w[1].partial = p2; w[1].out_w = d_down_w; w[1].sc = 1; w[1].sj = D;
-    w[1].alpha = 1.0f; w[1].out_xsum = nullptr; w[1].alpha_x = 0.f; w[1].out_ysum = d_down_b; w[1].alpha_y = 1.0f;
+    w[1].alpha = inv_dw; w[1].out_xsum = nullptr; w[1].alpha_x = 0.f; w[1].out_ysum = d_down_b; w[1].alpha_y = inv_dw;   // Y = ddz: 2^(ed + ew)
     rc = launch_wgrad(P, w, 2, s); if (rc) return rc;
     if (dx) {
-        GemmArgs a; a.A = ddz; a.W = o.down_wT; a.M = M; a.N = D; a.K = RP; a.out_f32 = dx; a.accumulate = 0;
+        GemmArgs a; a.A = ddz; a.W = o.down_wT; a.M = M; a.N = D; a.K = RP; a.out_f32 = dx; a.accumulate = 0; a.scale = inv_dw;
         rc = launch_gemm(P, EPI_STORE_F32, a, s); if (rc) return rc;
     }
     DYT_HIP_CHECK(hipStreamSynchronize(s));

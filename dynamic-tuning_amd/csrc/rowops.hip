@@ -1070,7 +1070,8 @@ __global__ __launch_bounds__(256) void tok_bwd_kernel(TokBwdArgs a) {
         TK_SCALPIN3(sf, dmk, dlg);
         if (cat) {
             DYT_PIN2(cd, cz);
-            if (a.maskf[t] != 0.f) dmk -= wave_sum(cd * cz) * a.cat_ddz_scale;   // dropped tokens have dmask = 0 and no saved h
+            const float czs = a.cat_ddz_dscale ? a.cat_ddz_scale * *a.cat_ddz_dscale : a.cat_ddz_scale;
+            if (a.maskf[t] != 0.f) dmk -= wave_sum(cd * cz) * czs;   // dropped tokens have dmask = 0 and no saved h
         }
         const float bs = a.branch_scale ? a.branch_scale[b] : 1.0f;   // stochastic depth on the MLP branch (uniform per image)
         dmk *= bs;
@@ -1477,6 +1478,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WgPair src, int M, int c
 
 struct WgOut {
     const float* partial; float* out_w; int sc, sj; float alpha; float* out_xsum; float alpha_x; float* out_ysum; float alpha_y;
+    const float* alpha_dev;
 };
 struct WgOutPair { WgOut p[2]; };
 __global__ void wgrad_reduce_kernel(WgOutPair outs, int nchunks, int r) {
@@ -1488,9 +1490,10 @@ __global__ void wgrad_reduce_kernel(WgOutPair outs, int nchunks, int r) {
     if (c == D && j == r) return;
     float acc = 0.f;
     for (int p = 0; p < nchunks; ++p) acc += o.partial[((size_t)p * WG_ROWS + c) * WG_J + col];
-    if (c == D) { if (o.out_ysum) o.out_ysum[j] += o.alpha_y * acc; }
-    else if (j < r) o.out_w[(size_t)c * o.sc + (size_t)j * o.sj] += o.alpha * acc;
-    else if (o.out_xsum) o.out_xsum[c] += o.alpha_x * acc;
+    const float ad = o.alpha_dev ? *o.alpha_dev : 1.0f;
+    if (c == D) { if (o.out_ysum) o.out_ysum[j] += (o.alpha_y * ad) * acc; }
+    else if (j < r) o.out_w[(size_t)c * o.sc + (size_t)j * o.sj] += (o.alpha * ad) * acc;
+    else if (o.out_xsum) o.out_xsum[c] += (o.alpha_x * ad) * acc;
 }
 
 // the reduce of several products (each with its own partial buffer and chunk count) in one launch: blockIdx.y selects the product
@@ -1504,9 +1507,10 @@ __global__ void wgrad_reduce_batch_kernel(WgReduceBatch b, int r) {
     if (c == D && j == r) return;
     float acc = 0.f;
     for (int p = 0; p < o.nchunks; ++p) acc += o.partial[((size_t)p * WG_ROWS + c) * WG_J + col];
-    if (c == D) { if (o.out_ysum) o.out_ysum[j] += o.alpha_y * acc; }
-    else if (j < r) o.out_w[(size_t)c * o.sc + (size_t)j * o.sj] += o.alpha * acc;
-    else if (o.out_xsum) o.out_xsum[c] += o.alpha_x * acc;
+    const float ad = o.alpha_dev ? *o.alpha_dev : 1.0f;
+    if (c == D) { if (o.out_ysum) o.out_ysum[j] += (o.alpha_y * ad) * acc; }
+    else if (j < r) o.out_w[(size_t)c * o.sc + (size_t)j * o.sj] += (o.alpha * ad) * acc;
+    else if (o.out_xsum) o.out_xsum[c] += (o.alpha_x * ad) * acc;
 }
 int flush_reductions(ReduceQueue& q, hipStream_t s) {
     if (q.n_wg > 0) {
@@ -1547,7 +1551,7 @@ int launch_wgrad(int precision, const WgradArgs* a, int n, hipStream_t s, Reduce
         const bool half = precision == 0 && w.half_products;
         const float xs = half ? w.x_scale : 1.f, ys = half ? w.y_scale : 1.f;
         src.p[i] = WgSrc{w.X, w.Y, w.partial, xs, ys};
-        outs.p[i] = WgOut{w.partial, w.out_w, w.sc, w.sj, w.alpha / (xs * ys), w.out_xsum, w.alpha_x / xs, w.out_ysum, w.alpha_y / ys};
+        outs.p[i] = WgOut{w.partial, w.out_w, w.sc, w.sj, w.alpha / (xs * ys), w.out_xsum, w.alpha_x / xs, w.out_ysum, w.alpha_y / ys, w.alpha_dev};
     }
     if (precision == 0 && a[0].half_products != (n == 2 ? a[1].half_products : a[0].half_products)) { set_error("launch_wgrad: mixed product forms in a pair"); return -1; }
     if (precision == 0 && a[0].half_products) hipLaunchKernelGGL(wgrad_bf16_kernel<float>, dim3(D / 128, nchunks, n), dim3(256), 0, s, src, M, chunk);
@@ -1567,7 +1571,7 @@ int launch_wgrad(int precision, const WgradArgs* a, int n, hipStream_t s, Reduce
         defer->r = r;
         for (int i = 0; i < n; ++i) {
             const WgOut& o = outs.p[i];
-            defer->wg[defer->n_wg++] = WgReduceDesc{o.partial, o.out_w, o.sc, o.sj, o.alpha, o.out_xsum, o.alpha_x, o.out_ysum, o.alpha_y, nchunks};
+            defer->wg[defer->n_wg++] = WgReduceDesc{o.partial, o.out_w, o.sc, o.sj, o.alpha, o.out_xsum, o.alpha_x, o.out_ysum, o.alpha_y, nchunks, o.alpha_dev};
         }
         LAUNCH_CHECK();
         return 0;

@@ -152,6 +152,36 @@ def add_adapter_layernorm(sd, seed=0, depth=DEPTH):
     return out
 
 
+def reference_adapter_init(sd, seed=0):
+    """The reference's own adapter init (``Adapter._init_weights``, ``models/dynamic_adapter.py:112-117``) on a copy of ``sd``:
+    ``down_proj.weight`` kaiming_uniform_(a=sqrt(5)), i.e. U(-1/sqrt(768), 1/sqrt(768)); ``up_proj.weight`` and both adapter biases
+    exactly 0.  Everything else (the frozen backbone, gates, head) is left as it is.  The adapter branch then contributes nothing to
+    the forward pass and the up_proj dgrad starts from an exact zero -- the first steps of a real run."""
+    out = dict(sd)
+    bound = 1.0 / np.sqrt(DIM)
+    for name, t in sd.items():
+        if ".adaptmlp.down_proj.weight" in name:
+            a = _rng(name + "/kaiming_uniform", seed).uniform(-bound, bound, size=tuple(t.shape))
+            out[name] = torch.from_numpy(a.astype(np.float32)).clamp_(-bound, bound).contiguous()
+        elif ".adaptmlp.up_proj.weight" in name or ".adaptmlp.down_proj.bias" in name or ".adaptmlp.up_proj.bias" in name:
+            out[name] = torch.zeros_like(t)
+    return out
+
+
+def scale_up_proj(sd, k, seed=0):
+    """A copy of ``sd`` with every ``up_proj.weight`` set to ``2^-k`` x a fixed N(0, 0.02) pattern (the one ``make_state_dict`` draws, so
+    k = 0 gives its values back); k = inf: exactly 0.  2^-k is exact in fp32 for the magnitudes used (|w| >= 1e-12), so the ladder
+    k = 0, 6, 12, ... is one matrix at falling magnitudes -- what up_proj passes through during the lr warm-up of a real run."""
+    out = dict(sd)
+    for name, t in sd.items():
+        if ".adaptmlp.up_proj.weight" in name:
+            if k == float("inf"):
+                out[name] = torch.zeros_like(t)
+            else:
+                out[name] = (_normal(name, tuple(t.shape), seed, 0.02) * (2.0 ** -k)).contiguous()
+    return out
+
+
 def make_batch(batch, num_classes=100, seed=0):
     """Images ``N(0,1)`` [B,3,224,224] fp32 and int64 targets."""
     x = _normal("images", (batch, 3, 224, 224), seed, 1.0)

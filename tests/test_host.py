@@ -302,3 +302,64 @@ def test_gradient_scale_backoff_and_growth_follow_gradscaler_update():
         counters[0] += 5
         opt.overflow_backoff(eng2)
     assert eng2.grad_scale_log2 == 14
+
+
+def test_reference_adapter_init_and_up_proj_ladder():
+    """synth.reference_adapter_init is the reference's Adapter._init_weights (models/dynamic_adapter.py:112-117): down_proj.weight
+    kaiming_uniform_(a=sqrt(5)) = U(+-1/sqrt(768)), up_proj.weight and both adapter biases exactly 0, nothing else touched; and
+    synth.scale_up_proj(k) is one fixed N(0, 0.02) pattern times exactly 2^-k (k = inf: exact zeros)."""
+    import math
+    import numpy as np
+    base = synth.make_state_dict(100, 64, kind="test")
+    sd = synth.reference_adapter_init(base, seed=0)
+    assert list(sd.keys()) == list(base.keys()) and len(sd) == 224
+    assert all(sd[k].shape == base[k].shape and sd[k].dtype == torch.float32 for k in sd)
+    bound = float(np.float32(1.0 / math.sqrt(768)))
+    for i in range(12):
+        p = "blocks.%d.adaptmlp." % i
+        w = sd[p + "down_proj.weight"]
+        assert float(w.abs().max()) <= bound and float(w.abs().max()) > 0.99 * bound
+        assert abs(float(w.double().mean())) < 0.02 * bound and abs(float(w.double().std()) / (bound / math.sqrt(3.0)) - 1.0) < 0.02
+        for n in ("up_proj.weight", "down_proj.bias", "up_proj.bias"):
+            assert sd[p + n].count_nonzero() == 0, n
+    untouched = [k for k in base if not any(s in k for s in ("down_proj.weight", "up_proj.weight", "down_proj.bias", "up_proj.bias"))]
+    assert len(untouched) == 224 - 48 and all(torch.equal(sd[k], base[k]) for k in untouched)
+    # the library's own Adapter module initialises the same way (zeros exactly; down_proj inside the kaiming bound)
+    m = _model()
+    ad = m.blocks[5].adaptmlp
+    assert float(ad.down_proj.weight.detach().abs().max()) <= bound and ad.up_proj.weight.count_nonzero() == 0
+    assert ad.down_proj.bias.count_nonzero() == 0 and ad.up_proj.bias.count_nonzero() == 0
+    # the ladder
+    assert all(torch.equal(synth.scale_up_proj(sd, 0)[k], base[k]) for k in base if "up_proj.weight" in k)
+    z = synth.scale_up_proj(sd, float("inf"))
+    assert all(z[k].count_nonzero() == 0 for k in z if "up_proj.weight" in k)
+    for k in (6, 12, 18, 24):
+        s = synth.scale_up_proj(sd, k)
+        assert list(s.keys()) == list(sd.keys())
+        for n in s:
+            if "up_proj.weight" in n:
+                assert torch.equal(s[n], base[n] * 2.0 ** -k) and s[n].count_nonzero() == s[n].numel()
+            else:
+                assert s[n] is sd[n]
+
+
+def test_oracle_is_sound_at_a_tiny_up_proj():
+    """The reference side of the GPU init ladder (tests/test_gpu_adapter_init.py): at up_proj = 2^-24 x N(0, 0.02) the fp32 oracle's
+    down_proj gradients (all about 2^-24 of their usual size) agree with the same oracle run in float64 to 1e-5 relative -- fp32 has
+    the exponent range, so the ladder measures the library, not its reference."""
+    B, C, r = 2, 100, 64
+    sd = synth.scale_up_proj(synth.reference_adapter_init(synth.make_state_dict(C, r, kind="test", gate_bias=0.85)), 24)
+    x, y = synth.make_batch(B, C, seed=5)
+    g1, g2 = synth.make_noise(B, seed=6)
+    keep = synth.make_dropout_masks(B, r, seed=7)
+    kw = dict(scale=0.1, mode="compact", token_target_ratio=0.5)
+    _, g32, (_, _, t32) = O.step_grads(sd, x, y, g1, g2, keep, **kw)
+    _, g64, (_, _, t64) = O.step_grads({k: v.double() for k, v in sd.items()}, x.double(), y, g1.double(), g2.double(), keep, **kw)
+    assert torch.equal(t32["token_select"].detach().float(), t64["token_select"].detach().float())   # same decisions: same function
+    worst = 0.0
+    for n in g32:
+        if "down_proj" in n:
+            e = float((g32[n].double() - g64[n]).norm() / g64[n].norm())
+            assert 0 < float(g64[n].norm()) and e <= 1e-5, (n, e)
+            worst = max(worst, e)
+    print("oracle fp32 vs fp64, down_proj gradients at up_proj ~ 2^-24: worst rel-L2 %.2e" % worst)
