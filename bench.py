@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the DyT ViT-B/16 fine-tune step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W        (N>1: starts N ranks itself, or runs as one rank
-                                                         when launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full]   (N>1: starts N ranks itself, or runs as one rank
+                                                             when launched by torch.distributed.run)
 
 One "step" = engine_finetune.py:47-79 of the reference: student forward (compacted MLP, Gumbel
 gate, adapter dropout), teacher forward (complete model), CE + 2*token-ratio + teacher CE + KL,
@@ -10,10 +10,13 @@ one backward over both passes, (all-reduce of the 5 MB trainable gradients), Ada
 of synthetic N(0,1) images resident in HBM, B=128 per GPU (configs[1] of BASELINE.json, the
 train_IN21K.sh shape), r=64, C=100, gate biases calibrated so the measured keep ratio is ~0.70.
 
-Prints ONE JSON line (rank 0).  Besides the driver's contract it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set up, warm up,
+time the K steps, write --dump-outputs, print.  With --full the line also carries
   roofline     -- the dominant kernel (the bf16 MFMA GEMM family, csrc/gemm.hip): algorithmic FLOPs of
                   its launches in one step / their summed duration, measured with HIP events on the
                   launch stream inside this process, against the dense bf16 MFMA peak (2.5 PFLOP/s);
+  host_enqueue_ms_per_step, host_fed (N=1), other_fast_mode / parity_mode / exact_mode (N=1) --
+                  the host's cost of a step, the host-fed loop, the other precisions (see main());
   cpu_baseline -- the CPU oracle (torch fp32 restatement of the reference, pinned to golden vectors)
                   running the same step at B=16 on the host cores (N=1, rank 0 only).
 """
@@ -148,8 +151,12 @@ def main():
     ap.add_argument("--classes", type=int, default=100)
     ap.add_argument("--ffn_num", type=int, default=64)
     ap.add_argument("--keep", type=float, default=0.7)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the second (fp32 parity mode) measurement at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check: the roofline's event-profiled step, the host "
+                         "enqueue cost, the comm-stream check (N > 1), and at N = 1 the host-fed loop, the other precisions and the CPU "
+                         "baseline.  Off: set up, warm up, time the steps, write --dump-outputs, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity-mode", action="store_true", help="with --full: skip the measurements in the other precisions at N=1")
     ap.add_argument("--hip-graph", type=int, default=0,
                     help="1: replay the step's forward+backward from a captured hipGraph.  Off by default: on ROCm 7.2 a replay "
                          "costs the host as much as the eager launches (DESIGN.md section 7) and the capture has to serialise "
@@ -157,7 +164,8 @@ def main():
     ap.add_argument("--host-batches", type=int, default=-1,
                     help="N > 0: after the resident-data measurement, feed N DISTINCT pinned host batches through engine_finetune.train_one_epoch "
                          "(the reference's loop: host -> device copy of every batch, reference engine_finetune.py:34-42; here prefetched on a copy "
-                         "stream) for --steps steps and report images/s beside `value` as `host_fed`.  -1 (default): 8 at N=1, 0 otherwise")
+                         "stream) for --steps steps and report images/s beside `value` as `host_fed`.  -1 (default): 8 with --full at N=1, "
+                         "0 otherwise")
     ap.add_argument("--video-frames", type=int, default=0,
                     help="T > 1: BASELINE.json configs[4] shape instead of the headline one -- the video model, "
                          "--batch frames per GPU = batch/T clips of T frames (train_video.sh: 16 clips x 8 frames, 400 classes)")
@@ -172,7 +180,7 @@ def main():
     if args.video_frames > 1:
         assert args.batch % args.video_frames == 0, "--batch must be a multiple of --video-frames"
     if args.host_batches < 0:
-        args.host_batches = 8 if (args.gpus == 1 and args.video_frames <= 1) else 0
+        args.host_batches = 8 if (args.full and args.gpus == 1 and args.video_frames <= 1) else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: start N ranks ourselves (one process per GPU over RCCL), exactly the command the
@@ -215,7 +223,7 @@ def main():
     assert world == args.gpus, "launch with torch.distributed.run --nproc-per-node %d" % args.gpus
 
     head = measure(args, args.precision, args.mode, args.steps, args.warmup, device, world, rank, host_batches=args.host_batches,
-                   dump_dir=args.dump_outputs)
+                   dump_dir=args.dump_outputs, full=args.full)
     side_errors = {}
 
     def side(name, *a, **kw):
@@ -234,7 +242,7 @@ def main():
     parity = None
     other = None
     exact = None
-    extras = world == 1 and args.video_frames <= 1 and args.precision in ("fp16", "bf16") and not args.no_parity_mode
+    extras = args.full and world == 1 and args.video_frames <= 1 and args.precision in ("fp16", "bf16") and not args.no_parity_mode
     if extras:
         # the other 16-bit operand type on the same workload (same kernels, same MFMA rate)
         torch.cuda.empty_cache()
@@ -323,8 +331,9 @@ def main():
         cores = [None] * world
         dist.all_gather_object(cores, synth.available_cores())
         dist_info = {"torch_world_size": world, "rccl_ranks": head.get("rccl_ranks"), "host_cores_per_rank": cores,
-                     "comm_stream_concurrent": head.get("comm_stream_concurrent"),
                      "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+        if args.full:
+            dist_info["comm_stream_concurrent"] = head.get("comm_stream_concurrent")
         dist.barrier()
 
     if rank == 0:
@@ -348,9 +357,11 @@ def main():
             "step_gflop_executed_per_image": head["step_gflop_executed_per_image"],
             "step_mfma_frac_executed": head["step_mfma_frac_executed"],
             "loss": head["loss"],
-            "host_enqueue_ms_per_step": head["host_enqueue_ms_per_step"],
-            "roofline": head["roofline"],
         }
+        if args.full:
+            out["host_enqueue_ms_per_step"] = head["host_enqueue_ms_per_step"]
+            out["roofline"] = head["roofline"]
+            log("roofline", head["roofline"])
         if head.get("host_fed") is not None:
             out["host_fed"] = head["host_fed"]
         if dist_info is not None:
@@ -363,8 +374,7 @@ def main():
             out["other_fast_mode"] = other
         if side_errors:
             out["side_measurement_errors"] = side_errors
-        log("roofline", head["roofline"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args)
             except Exception as e:   # noqa: BLE001 -- reported, never fatal for the line
@@ -448,9 +458,10 @@ def dump_outputs(dump_dir, model, losses):
     log("dumped %d arrays (%.1f MB) of the last timed step to %s" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6, dump_dir))
 
 
-def measure(args, precision, mode, steps, warmup, device, world, rank, host_batches=0, dump_dir=None):
-    """Build the model in one arithmetic / training mode, calibrate the keep ratio, time `steps` fused steps (barrier +
-    synchronize on both sides, max over ranks) and take the dominant-kernel roofline of one extra event-profiled step.
+def measure(args, precision, mode, steps, warmup, device, world, rank, host_batches=0, dump_dir=None, full=True):
+    """Build the model in one arithmetic / training mode, calibrate the keep ratio and time `steps` fused steps (barrier +
+    synchronize on both sides, max over ranks).  full: then also take the host's enqueue cost of two extra steps, the
+    dominant-kernel roofline of one extra event-profiled step and (N > 1) the comm-stream check.
     dump_dir: write what the last timed step returned (dump_outputs)."""
     from engine_finetune import FusedAdamW, train_step
     margs = argparse.Namespace(**vars(args))
@@ -495,31 +506,34 @@ def measure(args, precision, mode, steps, warmup, device, world, rank, host_batc
     dt = time.perf_counter() - t0
     if dump_dir is not None and rank == 0:   # before the extra steps below move the parameters again
         dump_outputs(dump_dir, model, last)
-    # host cost of a step: enqueue two steps into EMPTY queues (inside the timed loop the host runs ahead of the GPU until the
-    # hardware queues are full and then only measures back-pressure -- round 1's "13.6 ms" was that)
-    th0 = time.perf_counter()
-    for i in range(2):
-        one_step(10 ** 5 + i)
-    t_host = (time.perf_counter() - th0) / 2 * steps
-    torch.cuda.synchronize()
+    t_host = None
+    if full:
+        # host cost of a step: enqueue two steps into EMPTY queues (inside the timed loop the host runs ahead of the GPU until the
+        # hardware queues are full and then only measures back-pressure -- round 1's "13.6 ms" was that)
+        th0 = time.perf_counter()
+        for i in range(2):
+            one_step(10 ** 5 + i)
+        t_host = (time.perf_counter() - th0) / 2 * steps
+        torch.cuda.synchronize()
     tmax = torch.tensor([dt], device=device, dtype=torch.float64)
     if dist.is_initialized():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     host = (acc / steps).tolist()
-    log("[%s/%s] timed %d steps: %.2f ms/step (host enqueue %.2f ms/step)" % (precision, mode, steps, dt / steps * 1e3, t_host / steps * 1e3))
+    log("[%s/%s] timed %d steps: %.2f ms/step%s" % (precision, mode, steps, dt / steps * 1e3,
+                                                   " (host enqueue %.2f ms/step)" % (t_host / steps * 1e3) if full else ""))
     keep_meas = host[5]
 
     # dominant-kernel roofline: HIP events around every GEMM launch of ONE step (same stream)
     roof = None
     traffic = None
-    if precision in ("bf16", "fp16"):
+    if full and precision in ("bf16", "fp16"):
         try:  # HBM bytes per GEMM launch from the committed PMC passes of this same command (tools/pmc_traffic.py)
             with open(os.path.join(ROOT, "profiles", TRAFFIC_JSON)) as f:
                 traffic = json.load(f)
         except Exception:
             pass
-    if rank == 0:
+    if full and rank == 0:
         use_graph = False   # the event-profiled step runs eagerly, one stream
         eng.profile(True)
         # N > 1: forward + backward only -- this step runs on rank 0 ALONE, and the update leg holds the gradient all-reduce -- a collective the other
@@ -581,7 +595,7 @@ def measure(args, precision, mode, steps, warmup, device, world, rank, host_batc
         gflop += 2 * 3 * 2 * (2 * 197 * 768 * 768) / 1e9
         gflop_exec = gflop - (0.231211 + 0.697172 + 2 * 0.059609 + 0.232391)   # no cls-only tail in the video model
     res = {"value": round(ips, 2), "ms_per_step": round(dt / steps * 1e3, 3), "steps": steps,
-           "host_enqueue_ms_per_step": round(t_host / steps * 1e3, 3), "keep_ratio_measured": round(keep_meas, 4),
+           "host_enqueue_ms_per_step": round(t_host / steps * 1e3, 3) if full else None, "keep_ratio_measured": round(keep_meas, 4),
            "keep_ratio_calibrated": round(keep_cal, 4), "loss": round(host[0], 4), "step_gflop_per_image": round(gflop, 3),
            "step_mfma_frac": round(ips / world * gflop * 1e9 / (PEAK[precision] * 1e12), 4),
            "step_gflop_executed_per_image": round(gflop_exec, 3),
@@ -591,7 +605,8 @@ def measure(args, precision, mode, steps, warmup, device, world, rank, host_batc
         import _lib
         comm = getattr(eng, "_rccl_comm", None)
         res["rccl_ranks"] = _lib.rccl_comm_ranks(comm) if comm is not None else None
-        res["comm_stream_concurrent"] = bool(eng.streams_concurrent(torch.cuda.current_stream(device), eng.comm_stream()))
+        if full:
+            res["comm_stream_concurrent"] = bool(eng.streams_concurrent(torch.cuda.current_stream(device), eng.comm_stream()))
     if host_batches > 0:
         try:   # a side measurement: it must never take the headline down with it (pinned allocations can be refused by a container's memlock limit)
             res["host_fed"] = host_fed(args, model, opt, steps, warmup, device, world, dt / steps * 1e3)

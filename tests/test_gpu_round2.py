@@ -685,7 +685,7 @@ def test_inference_speed_harness_runs():
 def test_bench_multi_rank_code_path_with_one_rank():
     """bench.py's N > 1 code path (RCCL process group, parameter broadcast, chunked all-reduce on the comm stream, barriers,
     max-over-ranks timing) with one rank (DYT_BENCH_FORCE_DIST=1): the one JSON line carries the driver's contract keys, the
-    BASELINE.json metric / config, a roofline measured in the same run, and the step is the full-size one."""
+    BASELINE.json metric / config, with --full a roofline measured in the same run, and the step is the full-size one."""
     import json
     import subprocess
     import sys
@@ -693,7 +693,7 @@ def test_bench_multi_rank_code_path_with_one_rank():
     env = dict(os.environ, DYT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-parity-mode"], capture_output=True, text=True, timeout=900, env=env)
+                          "--full", "--no-cpu-baseline", "--no-parity-mode"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -5,7 +5,7 @@ cd $root
 (cd /tmp && rocprofv3 -L 2>/dev/null | grep -i -E "MALL|DRAM|HBM|EA0_RDREQ|EA0_WRREQ" | head -40) > gpurun_out/r5_counter_list.txt 2>&1
 bash tools/pmc_bench.sh r5 > /dev/null 2>&1
 cp gpurun_out/r5_gemm_traffic.json profiles/round5/gemm_traffic.json 2>/dev/null
-python bench.py > gpurun_out/r5_final_benchline.json 2> gpurun_out/r5_final_benchline.err
+python bench.py --full > profiles/round5/r5_final_benchline.json
 bash tools/rocprof_bench.sh r5_final -- --steps 5 --warmup 2 --no-cpu-baseline --no-parity-mode > /dev/null 2>&1
 bash tools/rocprof_bench.sh r5_final_serial DYT_NO_OVERLAP=1 -- --steps 5 --warmup 2 --no-cpu-baseline --no-parity-mode > /dev/null 2>&1
 for p in fp16x3q fp32; do
