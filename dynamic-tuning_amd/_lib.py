@@ -83,11 +83,26 @@ class Config(ctypes.Structure):
     _fields_ = [("num_classes", ctypes.c_int32), ("ffn_num", ctypes.c_int32), ("depth", ctypes.c_int32),
                 ("precision", ctypes.c_int32), ("max_batch", ctypes.c_int32), ("slots", ctypes.c_int32),
                 ("adapter_scale", ctypes.c_float), ("adapter_dropout", ctypes.c_float), ("tau", ctypes.c_float),
-                ("threshold", ctypes.c_float), ("frames", ctypes.c_int32), ("adapter_ln", ctypes.c_int32)]
+                ("threshold", ctypes.c_float), ("frames", ctypes.c_int32), ("adapter_ln", ctypes.c_int32),
+                ("inference_only", ctypes.c_int32)]   # ABI v3: eval forwards only, without the training arena
 
 
 class DyTError(RuntimeError):
     pass
+
+
+def inference_only_default(explicit=None, tuning_config=None):
+    """The models' ``inference_only`` keyword: the explicit value, else ``tuning_config.dyt_inference_only``, else the environment's
+    DYT_INFERENCE_ONLY, else False."""
+    if explicit is not None:
+        return bool(explicit)
+    try:
+        v = getattr(tuning_config, "dyt_inference_only")
+    except (AttributeError, KeyError):
+        v = None
+    if v is not None:
+        return bool(v)
+    return os.environ.get("DYT_INFERENCE_ONLY", "0").strip().lower() not in ("", "0", "false", "no", "off")
 
 
 _lib = None

@@ -935,7 +935,8 @@ __device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, bf16x8&
 }
 // PARTS = 1: the hi * hi product alone for S and P V (IEEE-half attention on the same planes, fp32 softmax): the complete_model pass of
 // "fp16x3q", whose output no token-keep decision depends on (its budget is the 1e-3 logit bar, not the gate's 1e-5)
-template <bool PLANES, int PARTS = 3>   // PLANES: q / k / v arrive as 16-bit hi (q16 / k16 / v16) + lo planes written by the QKV epilogue: staged without conversion
+// LSE = false: the no-save variant (inference-only contexts; `lse` is null): the backward's row statistics are neither computed nor stored
+template <bool PLANES, int PARTS = 3, bool LSE = true>   // PLANES: q / k / v arrive as 16-bit hi (q16 / k16 / v16) + lo planes written by the QKV epilogue: staged without conversion
 __global__ __launch_bounds__(448) void attn_fwd_split_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                              const float* __restrict__ v, float* __restrict__ out,
                                                              float* __restrict__ lse, int nheads, bf16* __restrict__ out3,
@@ -1095,7 +1096,7 @@ __global__ __launch_bounds__(448) void attn_fwd_split_kernel(const float* __rest
         }
         float sum = (sp[0] + sp[1]) + (sp[2] + sp[3]);
         sum += __shfl_xor(sum, 32, 64);
-        if (hi == 0 && qrow < NT) lse[(size_t)bh * NT + qrow] = m + logf(sum);
+        if constexpr (LSE) { if (hi == 0 && qrow < NT) lse[(size_t)bh * NT + qrow] = m + logf(sum); }
         if (qrow < NT) {
             const float inv = 1.0f / sum;
             float* op = out ? out + ((size_t)b * NT + qrow) * D + h * HD : nullptr;
@@ -1415,7 +1416,8 @@ int launch_attn_fwd(int precision, const void* q, const void* k, const void* v, 
         if (hipGetDevice(&dev) != hipSuccess) dev = 0;
         if (!done[dev & 63]) {
             if (set_lds((const void*)attn_fwd_split_kernel<false>, lds) || set_lds((const void*)attn_fwd_split_kernel<true>, lds) ||
-                set_lds((const void*)attn_fwd_split_kernel<true, 1>, lds)) return -2;
+                set_lds((const void*)attn_fwd_split_kernel<true, 1>, lds) || set_lds((const void*)attn_fwd_split_kernel<false, 3, false>, lds) ||
+                set_lds((const void*)attn_fwd_split_kernel<true, 3, false>, lds) || set_lds((const void*)attn_fwd_split_kernel<true, 1, false>, lds)) return -2;
             done[dev & 63] = true;
         }
         if (parts != 3 && !(save16 && save16->q_lo && parts == 1)) { set_error("attention forward: the one-part form needs the planar q / k / v"); return -1; }
@@ -1423,18 +1425,25 @@ int launch_attn_fwd(int precision, const void* q, const void* k, const void* v, 
         // round-5 16-bit kernel on the hi planes, its result split on the way out (DYT_OPT_ATTN_V2 bit 0)
         if (save16 && save16->q_lo && parts == 1 && !out && out3 && out3_f8 && !save16->o && (get_attn_v2() & 1))
             return launch_attn_fwd_v2(save16->q, save16->k, save16->v, out3, lse, batch, s, 1);
+        // lse == null (inference-only contexts): the no-save variants
+        auto* k_p1 = lse ? attn_fwd_split_kernel<true, 1> : attn_fwd_split_kernel<true, 1, false>;
+        auto* k_p3 = lse ? attn_fwd_split_kernel<true> : attn_fwd_split_kernel<true, 3, false>;
+        auto* k_f32 = lse ? attn_fwd_split_kernel<false> : attn_fwd_split_kernel<false, 3, false>;
         if (save16 && save16->q_lo && parts == 1)
-            hipLaunchKernelGGL((attn_fwd_split_kernel<true, 1>), dim3(min(grid, 256)), dim3(448), lds, s, nullptr, nullptr, nullptr, (float*)out, lse, grid,
+            hipLaunchKernelGGL(k_p1, dim3(min(grid, 256)), dim3(448), lds, s, nullptr, nullptr, nullptr, (float*)out, lse, grid,
                                (bf16*)out3, (bf16*)save16->q, (bf16*)save16->k, (bf16*)save16->v, (bf16*)save16->o, out3_f8,
                                (const bf16*)save16->q_lo, (const bf16*)save16->k_lo, (const bf16*)save16->v_lo);
         else if (save16 && save16->q_lo)
-            hipLaunchKernelGGL(attn_fwd_split_kernel<true>, dim3(min(grid, 256)), dim3(448), lds, s, nullptr, nullptr, nullptr, (float*)out, lse, grid,
+            hipLaunchKernelGGL(k_p3, dim3(min(grid, 256)), dim3(448), lds, s, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)out, lse, grid,
                                (bf16*)out3, (bf16*)save16->q, (bf16*)save16->k, (bf16*)save16->v, (bf16*)save16->o, out3_f8,
                                (const bf16*)save16->q_lo, (const bf16*)save16->k_lo, (const bf16*)save16->v_lo);
         else
-        hipLaunchKernelGGL(attn_fwd_split_kernel<false>, dim3(min(grid, 256)), dim3(448), lds, s, (const float*)q, (const float*)k,
+        hipLaunchKernelGGL(k_f32, dim3(min(grid, 256)), dim3(448), lds, s, (const float*)q, (const float*)k,
                            (const float*)v, (float*)out, lse, grid, (bf16*)out3, save16 ? (bf16*)save16->q : nullptr, save16 ? (bf16*)save16->k : nullptr,
                            save16 ? (bf16*)save16->v : nullptr, save16 ? (bf16*)save16->o : nullptr, out3_f8, nullptr, nullptr, nullptr);
+    } else if (!lse && !(precision != 0 && (get_attn_v2() & 1))) {   // (the exact-fp32 kernel and the round-4 16-bit kernel have no no-save variant: their callers pass the buffer)
+        set_error("attention forward: this kernel writes lse");
+        return -1;
     } else if (precision == 0) {
         if (out3) { set_error("attention forward: split output without the split kernel"); return -1; }
         const size_t lds = F_IMG + NPAD * HD * sizeof(float);

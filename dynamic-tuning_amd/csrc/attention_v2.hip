@@ -199,7 +199,9 @@ __device__ __forceinline__ uint2 e4m3x8(const uint4& h8) {   // 8 packed 16-bit 
     r.y = (unsigned)pack4_e4m3((float)x[4], (float)x[5], (float)x[6], (float)x[7]);
     return r;
 }
-template <bool PIPE, int ABL = 0, bool OUT3 = false>
+// LSE = false: the no-save variant of an inference-only context -- the log-sum-exp row statistics exist for the backward pass alone, so
+// neither the logarithm nor the store is issued (`lse` is null); the output rows are computed by the same instructions
+template <bool PIPE, int ABL = 0, bool OUT3 = false, bool LSE = true>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v2_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                                                              const bf16* __restrict__ v, bf16* __restrict__ out,
                                                              float* __restrict__ lse, int nheads) {
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v2_kernel(const bf16* __restr
         const float l = (l4[0] + l4[1]) + (l4[2] + l4[3]);
         const float sum = xhalf_sum(l);
         if (ABL & 1) { if (sum == 123.456f) lse[0] = o[0][0] + o[1][5] + s[3]; continue; }
-        if (hi == 0 && qrow < NT) lse[(size_t)bh * NT + qrow] = (m + __builtin_amdgcn_logf(sum)) * (1.0f / LOG2E);
+        if constexpr (LSE) { if (hi == 0 && qrow < NT) lse[(size_t)bh * NT + qrow] = (m + __builtin_amdgcn_logf(sum)) * (1.0f / LOG2E); }
         // O^T tile -> whole 128-byte rows of `out` (pack_rows above)
         const float inv = 1.0f / sum;
         f32x16 on[2];
@@ -671,16 +673,20 @@ int launch_attn_fwd_v2(const void* q, const void* k, const void* v, void* out, f
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     if (!done[dev & 63]) {
         if (set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true>, lds) || set_lds_v2((const void*)av2::attn_fwd_v2_kernel<false>, lds) ||
-            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true>, lds)) return -2;
+            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true>, lds) ||
+            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, false, false>, lds) || set_lds_v2((const void*)av2::attn_fwd_v2_kernel<false, 0, false, false>, lds) ||
+            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true, false>, lds)) return -2;
         done[dev & 63] = true;
     }
     if (out3_f8) {   // `out` = the proj GEMM's operand image in the hi16 / fp8 form
-        hipLaunchKernelGGL((av2::attn_fwd_v2_kernel<true, 0, true>), dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
+        auto* kern3 = lse ? av2::attn_fwd_v2_kernel<true, 0, true> : av2::attn_fwd_v2_kernel<true, 0, true, false>;   // lse == null: the no-save variant
+        hipLaunchKernelGGL(kern3, dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                            (bf16*)out, lse, grid);
         DYT_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    auto* kern = pipe ? av2::attn_fwd_v2_kernel<true> : av2::attn_fwd_v2_kernel<false>;
+    auto* kern = lse ? (pipe ? av2::attn_fwd_v2_kernel<true> : av2::attn_fwd_v2_kernel<false>)
+                     : (pipe ? av2::attn_fwd_v2_kernel<true, 0, false, false> : av2::attn_fwd_v2_kernel<false, 0, false, false>);
     hipLaunchKernelGGL(kern, dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, lse, grid);
     DYT_HIP_CHECK(hipGetLastError());
     return 0;

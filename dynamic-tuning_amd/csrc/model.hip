@@ -59,13 +59,13 @@ __global__ void prep_adapters_kernel(const float* __restrict__ flat, int64_t lay
         const float dw = j < r ? base[off_dw + (int64_t)j * D + c] : 0.f;   // down_proj.weight [r,768]
         const float uw = j < r ? ls * base[off_uw + (int64_t)c * r + j] : 0.f;   // up_proj.weight [768,r]
         down_w[(size_t)l * SZ + idx] = from_f32<AT>(dw);
-        up_wT[(size_t)l * SZ + idx] = from_f32<AT>(up_t_lift ? uw * up_t_lift[l] : uw);
+        if (up_wT) up_wT[(size_t)l * SZ + idx] = from_f32<AT>(up_t_lift ? uw * up_t_lift[l] : uw);   // (null, like down_wT: inference-only contexts)
     }
     {   // idx -> (c, j) of [768,RP]
         const int c = idx / RP, j = idx - c * RP;
         const float dw = j < r ? base[off_dw + (int64_t)j * D + c] : 0.f;
         const float uw = j < r ? ls * base[off_uw + (int64_t)c * r + j] : 0.f;
-        down_wT[(size_t)l * SZ + idx] = from_f32<AT>(dw);
+        if (down_wT) down_wT[(size_t)l * SZ + idx] = from_f32<AT>(dw);
         up_w[(size_t)l * SZ + idx] = from_f32<AT>(uw);
         if (up_ws) up_ws[(size_t)l * SZ + idx] = from_f32<AT>(scale * uw);
     }
@@ -186,6 +186,7 @@ struct LayerS {  // saved activations of one pass
 };
 struct Transients {  // scratch of one pass (per slot, so two passes can run on two streams)
     void *xn, *h1, *g_at, *dZ, *ddz, *du_at, *dO, *dqkv, *dA2, *dxn, *dad;
+    float* sk_ws = nullptr;   // inference-only contexts: the split-K workspace of the cls-only last block's fc2 (a training context lends it T.dZ)
     void* dact_s = nullptr;   // 16-bit modes: adapter_scale * d_act, the A2 operand of the fc2 + up-projection contraction
     void* dact3 = nullptr;    // 16-bit-backward split modes: the same as a [M][hi 64 | lo 64] image (three-part up-projection, alone or as the fc2 GEMM's leading tiles)
     void* a3 = nullptr;   // fp32 mode: [M, 3 * 3072] 16-bit scratch for the split A operand of a GEMM
@@ -239,6 +240,9 @@ struct ProfRec { int cat; double flops; hipEvent_t a, b; const int* m_dev; int M
 
 struct dyt_ctx {
     dyt_config cfg;
+    // dyt_config::inference_only: one aliased LayerS, one slot, two residual streams, forward transients and forward weight images only
+    // (layout / layout_aux); every entry point that needs more refuses (refuse_inference)
+    bool inf = false;
     int prec;
     size_t at;  // bytes per activation element
     char* arena = nullptr;
@@ -349,6 +353,11 @@ static void* carve_at(dyt_ctx* c, size_t count, bool dry) {
 static void layout(dyt_ctx* c, bool dry) {
     const dyt_config& cf = c->cfg;
     const size_t B = cf.max_batch, M = B * NT, depth = cf.depth, C = cf.num_classes;
+    // inference-only contexts (dyt_ctx::inf) carve nothing that only the backward pass / the optimizer entries read: bwd_at / bwd_f32 return null there
+    // (in a training context they carve in place, so its layout is byte for byte what it was)
+    const bool inf = c->inf;
+    auto bwd_at = [&](size_t n) -> void* { return inf ? nullptr : carve_at(c, n, dry); };
+    auto bwd_f32 = [&](size_t n) -> float* { return inf ? nullptr : carve<float>(c, n, dry); };
     c->arena_used = 0;
     c->cls = carve<float>(c, D, dry);
     c->pos = carve<float>(c, NT * D, dry);
@@ -363,15 +372,15 @@ static void layout(dyt_ctx* c, bool dry) {
         w.ln2_w = carve<float>(c, D, dry); w.ln2_b = carve<float>(c, D, dry);
         w.qkv_b = carve<float>(c, 3 * D, dry); w.proj_b = carve<float>(c, D, dry);
         w.fc1_b = carve<float>(c, DM, dry); w.fc2_b = carve<float>(c, D, dry);
-        w.qkv_w = carve_at(c, (size_t)3 * D * D, dry); w.qkv_wT = carve_at(c, (size_t)3 * D * D, dry);
-        w.proj_w = carve_at(c, (size_t)D * D, dry); w.proj_wT = carve_at(c, (size_t)D * D, dry);
-        w.fc1_w = carve_at(c, (size_t)DM * D, dry); w.fc1_wT = carve_at(c, (size_t)DM * D, dry);
-        w.fc2_w = carve_at(c, (size_t)DM * D, dry); w.fc2_wT = carve_at(c, (size_t)DM * D, dry);
+        w.qkv_w = carve_at(c, (size_t)3 * D * D, dry); w.qkv_wT = bwd_at((size_t)3 * D * D);
+        w.proj_w = carve_at(c, (size_t)D * D, dry); w.proj_wT = bwd_at((size_t)D * D);
+        w.fc1_w = carve_at(c, (size_t)DM * D, dry); w.fc1_wT = bwd_at((size_t)DM * D);
+        w.fc2_w = carve_at(c, (size_t)DM * D, dry); w.fc2_wT = bwd_at((size_t)DM * D);
         if (c->prec != 0) {
             w.qkv_wp = carve_at(c, (size_t)3 * D * D, dry); w.fc1_wp = carve_at(c, (size_t)DM * D, dry);
-            w.fc2_wTp = carve_at(c, (size_t)DM * D, dry);
-            w.proj_wp = carve_at(c, (size_t)D * D, dry); w.proj_wTp = carve_at(c, (size_t)D * D, dry);
-            w.qkv_wTp = carve_at(c, (size_t)3 * D * D, dry); w.fc1_wTp = carve_at(c, (size_t)DM * D, dry);
+            w.fc2_wTp = bwd_at((size_t)DM * D);
+            w.proj_wp = carve_at(c, (size_t)D * D, dry); w.proj_wTp = bwd_at((size_t)D * D);
+            w.qkv_wTp = bwd_at((size_t)3 * D * D); w.fc1_wTp = bwd_at((size_t)DM * D);
             if (c->ln_fold) {
                 w.fc1_wf = carve_at(c, (size_t)DM * D, dry); w.fc1_wfp = carve_at(c, (size_t)DM * D, dry);
                 w.fc1_cs = carve<float>(c, DM, dry); w.fc1_bf = carve<float>(c, DM, dry); w.fc1_w32 = carve<float>(c, (size_t)DM * D, dry);
@@ -379,25 +388,31 @@ static void layout(dyt_ctx* c, bool dry) {
         }
     }
     c->ad_down_w = carve_at(c, depth * RP * D, dry);
-    c->ad_down_wT = carve_at(c, depth * RP * D, dry);
+    c->ad_down_wT = bwd_at(depth * RP * D);
     c->ad_up_w = carve_at(c, depth * RP * D, dry);
-    c->ad_up_wT = carve_at(c, depth * RP * D, dry);
+    c->ad_up_wT = bwd_at(depth * RP * D);
     c->ad_down_b = carve<float>(c, depth * RP, dry);
-    c->ad_lift = carve<float>(c, 2 * depth, dry);
-    c->slots.resize(cf.slots);
-    for (int s = 0; s < cf.slots; ++s) {
+    c->ad_lift = bwd_f32(2 * depth);
+    const int nslots = inf ? 1 : cf.slots;   // inference-only: every slot index runs in the one slot (forward_impl)
+    c->slots.resize(nslots);
+    for (int s = 0; s < nslots; ++s) {
         Slot& S = c->slots[s];
         S.L.resize(depth);
         S.xs.resize(depth + 1);
+        if (inf) {   // block l reads xs[l] and writes xs[l + 1]; nothing reads xs[l] once block l is through: two streams in turn
+            float* pp[2] = {carve<float>(c, M * D, dry), carve<float>(c, M * D, dry)};
+            for (size_t l = 0; l <= depth; ++l) S.xs[l] = pp[l & 1];
+        } else
         for (size_t l = 0; l <= depth; ++l) S.xs[l] = carve<float>(c, M * D, dry);
         S.counts = carve<int>(c, depth * B, dry);
         S.ucls_at = carve_at(c, B * D, dry);
-        S.gcls = carve<float>(c, B * D, dry);
+        S.gcls = bwd_f32(B * D);
         S.cls_n = carve<float>(c, B * D, dry);
         S.head_stats = carve<float2>(c, B, dry);
         for (size_t l = 0; l < depth; ++l) {
             LayerS& L = S.L[l];
-            L.st1 = carve<float2>(c, M, dry); L.st2 = carve<float2>(c, M, dry);
+            if (inf && l > 0) { L = S.L[0]; continue; }   // one set of per-block buffers: every block's launches run in stream order, each rewrites what it reads
+            L.st1 = inf ? nullptr : carve<float2>(c, M, dry); L.st2 = carve<float2>(c, M, dry);   // (LN1's statistics are the backward's: ln_fwd skips the store on null)
             if (c->ad_ln) L.st_a = carve<float2>(c, M, dry);
             if (c->ad_ln == 2) L.up32 = carve<float>(c, M * D, dry);
             L.q = carve_at(c, M * D, dry); L.k = carve_at(c, M * D, dry); L.v = carve_at(c, M * D, dry);
@@ -406,78 +421,80 @@ static void layout(dyt_ctx* c, bool dry) {
             L.u = carve<float>(c, M * D, dry);
             L.u_at = c->prec == 0 ? (void*)L.u : carve_at(c, M * D, dry);
             if (c->prec != 0 && c->ln_fold) L.ln_part = carve<float2>(c, M * LN_PARTS, dry);
-            L.z = carve_at(c, M * DM, dry);
+            L.z = bwd_at(M * DM);      // (an eval forward stores neither gelu'(z) nor the MLP output h: forward_impl passes null for both)
             L.d_act = carve_at(c, M * RP, dry);
-            L.h = carve_at(c, M * D, dry);
+            L.h = bwd_at(M * D);
             L.soft = carve<float>(c, M, dry); L.maskf = carve<float>(c, M, dry);
             L.keep_local = carve<int>(c, M, dry); L.offsets = carve<int>(c, B, dry);
             L.total = carve<int>(c, 4, dry); L.row_src = carve<int>(c, M, dry); L.dst_of = carve<int>(c, M, dry);
         }
     }
     if (c->frames > 1) {
-        c->pk_w = carve_at(c, (size_t)D * D, dry); c->pk_wT = carve_at(c, (size_t)D * D, dry);
-        c->pv_w = carve_at(c, (size_t)D * D, dry); c->pv_wT = carve_at(c, (size_t)D * D, dry);
+        c->pk_w = carve_at(c, (size_t)D * D, dry); c->pk_wT = bwd_at((size_t)D * D);
+        c->pv_w = carve_at(c, (size_t)D * D, dry); c->pv_wT = bwd_at((size_t)D * D);
         const size_t clips = B / c->frames;
-        for (int sl = 0; sl < cf.slots; ++sl) {
+        for (int sl = 0; sl < nslots; ++sl) {
             PoolS& Q = c->slots[sl].pool;
             Q.xf = carve<float>(c, M * D, dry);
             Q.st_f = carve<float2>(c, M, dry); Q.st_kv = carve<float2>(c, M, dry);
             Q.xk = carve_at(c, M * D, dry); Q.xv = carve_at(c, M * D, dry);
             Q.Kp = carve_at(c, M * D, dry); Q.Vp = carve_at(c, M * D, dry);
             const size_t Mp = (M + 63) / 64 * 64;
-            Q.dKt = carve_at(c, Mp * D, dry); Q.xkt = carve_at(c, Mp * D, dry);
-            Q.dVt = carve_at(c, Mp * D, dry); Q.xvt = carve_at(c, Mp * D, dry);
+            Q.dKt = bwd_at(Mp * D); Q.xkt = bwd_at(Mp * D);
+            Q.dVt = bwd_at(Mp * D); Q.xvt = bwd_at(Mp * D);
             Q.P = carve<float>(c, B * NH * NT, dry);
             Q.o = carve<float>(c, clips * D, dry); Q.y = carve<float>(c, clips * D, dry);
-            Q.dy = carve<float>(c, clips * D, dry); Q.dO = carve<float>(c, clips * D, dry);
-            Q.dq_part = carve<float>(c, clips * D, dry);
+            Q.dy = bwd_f32(clips * D); Q.dO = bwd_f32(clips * D);
+            Q.dq_part = bwd_f32(clips * D);
             Q.qn = carve<float>(c, D, dry); Q.qhat = carve<float>(c, D, dry); Q.qs = carve<float>(c, D, dry);
-            Q.gq = carve<float>(c, D, dry); Q.dqn = carve<float>(c, D, dry); Q.st_q = carve<float>(c, 4, dry);
+            Q.gq = bwd_f32(D); Q.dqn = bwd_f32(D); Q.st_q = carve<float>(c, 4, dry);
         }
     }
-    for (int sl = 0; sl < cf.slots; ++sl) {
+    for (int sl = 0; sl < nslots; ++sl) {
         Transients& T = c->slots[sl].T;
         T.xn = carve_at(c, M * D, dry);
         if (c->prec != 0 && c->ln_fold) { T.st_compact = carve<float2>(c, M, dry); T.drop_src = carve<int>(c, M, dry); }
         T.h1 = carve_at(c, M * DM, dry);
-        T.g_at = carve_at(c, M * D, dry);
-        T.dZ = carve_at(c, M * DM, dry);
-        T.ddz = carve_at(c, M * RP, dry);
-        T.du_at = carve_at(c, M * D, dry);
-        T.dad = c->prec != DYT_PREC_FP32 ? carve_at(c, M * D, dry) : nullptr;
+        T.g_at = bwd_at(M * D);
+        T.dZ = bwd_at(M * DM);
+        // (the forward borrows T.dZ as the split-K workspace of the last block's cls-only fc2: [K / 256 + 1 slices][B][768] fp32 of its own here)
+        if (inf) T.sk_ws = carve<float>(c, (size_t)(DM / 256 + 1) * B * D, dry);
+        T.ddz = bwd_at(M * RP);
+        T.du_at = bwd_at(M * D);
+        T.dad = c->prec != DYT_PREC_FP32 ? bwd_at(M * D) : nullptr;
         T.dact_s = c->prec != DYT_PREC_FP32 ? carve_at(c, M * RP, dry) : nullptr;
-        T.dO = carve_at(c, M * D, dry);
-        T.dqkv = carve_at(c, M * 3 * D, dry);
-        T.dA2 = carve_at(c, M * D, dry);
-        T.dxn = carve_at(c, M * D, dry);
-        T.g = carve<float>(c, M * D, dry);
-        T.delta = carve<float>(c, B * NH * NT, dry);
-        T.dmask = carve<float>(c, M, dry);
+        T.dO = bwd_at(M * D);
+        T.dqkv = bwd_at(M * 3 * D);
+        T.dA2 = bwd_at(M * D);
+        T.dxn = bwd_at(M * D);
+        T.g = bwd_f32(M * D);
+        T.delta = bwd_f32(B * NH * NT);
+        T.dmask = bwd_f32(M);
         if (c->ad_ln) {
-            T.xa = carve<float>(c, M * D, dry); T.dup = carve<float>(c, M * D, dry);
-            T.aln_part = carve<float>(c, (size_t)ln_param_grad_scratch_floats((int)M), dry);
+            T.xa = carve<float>(c, M * D, dry); T.dup = bwd_f32(M * D);
+            T.aln_part = bwd_f32((size_t)ln_param_grad_scratch_floats((int)M));
         }
-        T.tok_partial = carve<float>(c, ((M + 31) / 32) * (D + 1), dry);
-        T.wg_partial = carve<float>(c, ((M + 511) / 512) * (size_t)(D + 8) * 80, dry);
-        T.wg_partial2 = carve<float>(c, ((M + 511) / 512) * (size_t)(D + 8) * 80, dry);
+        T.tok_partial = bwd_f32(((M + 31) / 32) * (D + 1));
+        T.wg_partial = bwd_f32(((M + 511) / 512) * (size_t)(D + 8) * 80);
+        T.wg_partial2 = bwd_f32(((M + 511) / 512) * (size_t)(D + 8) * 80);
         Slot& S = c->slots[sl];
-        S.dp_own = carve<float>(c, 2 * depth * B, dry);
-        S.gscr = carve<float>(c, (size_t)depth * c->layer_stride, dry);
+        S.dp_own = bwd_f32(2 * depth * B);   // (stochastic depth belongs to training passes: dyt_set_drop_path refuses)
+        S.gscr = bwd_f32((size_t)depth * c->layer_stride);
         S.wg_part.resize(depth); S.wg_part2.resize(depth); S.tok_part.resize(depth);
         for (size_t l = 0; l < depth; ++l) {
-            S.wg_part[l] = carve<float>(c, ((M + 511) / 512) * (size_t)(D + 8) * 80, dry);
-            S.wg_part2[l] = carve<float>(c, ((M + 511) / 512) * (size_t)(D + 8) * 80, dry);
-            S.tok_part[l] = carve<float>(c, ((M + 31) / 32) * (D + 1), dry);
+            S.wg_part[l] = bwd_f32(((M + 511) / 512) * (size_t)(D + 8) * 80);
+            S.wg_part2[l] = bwd_f32(((M + 511) / 512) * (size_t)(D + 8) * 80);
+            S.tok_part[l] = bwd_f32(((M + 31) / 32) * (D + 1));
         }
     }
-    c->grad2 = carve<float>(c, (size_t)c->n_train, dry);
+    c->grad2 = bwd_f32((size_t)c->n_train);
     c->ad_up_bp = carve<float>(c, depth * D, dry);
     if (c->ad_ln == 2) c->ad_up_ws = carve_at(c, depth * RP * D, dry);
     c->cls_rows = carve<int>(c, B, dry);
     c->seed_dev = carve<uint64_t>(c, 2, dry);
-    c->clip_scratch = carve<float>(c, 256, dry);
-    c->dl_s = carve<float>(c, B * C, dry); c->dl_t = carve<float>(c, B * C, dry);
-    c->logits_s = carve<float>(c, B * C, dry); c->logits_t = carve<float>(c, B * C, dry);
+    c->clip_scratch = bwd_f32(256);
+    c->dl_s = bwd_f32(B * C); c->dl_t = bwd_f32(B * C);
+    c->logits_s = bwd_f32(B * C); c->logits_t = bwd_f32(B * C);
     c->dtok = carve<float>(c, 4, dry);
     c->loss_part = carve<float>(c, 4 * B, dry);
     c->losses = carve<float>(c, 8, dry);
@@ -489,6 +506,8 @@ static void layout(dyt_ctx* c, bool dry) {
 static void layout_aux(dyt_ctx* c, bool dry, bool bwd16) {
     const dyt_config& cf = c->cfg;
     const size_t B = cf.max_batch, M = B * NT, depth = cf.depth, SA = SPLIT_A;
+    const bool inf = c->inf;   // inference-only: the forward's images and operand scratch alone, one set of per-block planes (as layout)
+    auto bwd16_u16 = [&](size_t n) -> void* { return inf ? nullptr : (void*)carve<uint16_t>(c, n, dry); };
     c->arena_used = 0;
     c->pe_w3 = carve<uint16_t>(c, SA * D * D, dry);
     c->pe_w_exp = carve<int>(c, 4, dry);
@@ -500,24 +519,24 @@ static void layout_aux(dyt_ctx* c, bool dry, bool bwd16) {
             w.qkv_w3b = carve<uint16_t>(c, SA * 3 * D * D, dry); w.proj_w3b = carve<uint16_t>(c, SA * D * D, dry);
             w.fc1_w3b = carve<uint16_t>(c, SA * DM * D, dry); w.fc2_w3b = carve<uint16_t>(c, SA * DM * D, dry);
         }
-        w.qkv_w3 = carve<uint16_t>(c, SA * 3 * D * D, dry); w.qkv_wT3 = carve<uint16_t>(c, SA * 3 * D * D, dry);
-        w.proj_w3 = carve<uint16_t>(c, SA * D * D, dry); w.proj_wT3 = carve<uint16_t>(c, SA * D * D, dry);
-        w.fc1_w3 = carve<uint16_t>(c, SA * DM * D, dry); w.fc1_wT3 = carve<uint16_t>(c, SA * DM * D, dry);
-        w.fc2_w3 = carve<uint16_t>(c, SA * DM * D, dry); w.fc2_wT3 = carve<uint16_t>(c, SA * DM * D, dry);
+        w.qkv_w3 = carve<uint16_t>(c, SA * 3 * D * D, dry); w.qkv_wT3 = bwd16_u16(SA * 3 * D * D);
+        w.proj_w3 = carve<uint16_t>(c, SA * D * D, dry); w.proj_wT3 = bwd16_u16(SA * D * D);
+        w.fc1_w3 = carve<uint16_t>(c, SA * DM * D, dry); w.fc1_wT3 = bwd16_u16(SA * DM * D);
+        w.fc2_w3 = carve<uint16_t>(c, SA * DM * D, dry); w.fc2_wT3 = bwd16_u16(SA * DM * D);
         if (bwd16) {
-            w.qkv_wT16 = carve<uint16_t>(c, (size_t)3 * D * D, dry); w.qkv_wTp16 = carve<uint16_t>(c, (size_t)3 * D * D, dry);
-            w.proj_wT16 = carve<uint16_t>(c, (size_t)D * D, dry); w.proj_wTp16 = carve<uint16_t>(c, (size_t)D * D, dry);
-            w.fc1_wT16 = carve<uint16_t>(c, (size_t)DM * D, dry); w.fc1_wTp16 = carve<uint16_t>(c, (size_t)DM * D, dry);
-            w.fc2_wT16 = carve<uint16_t>(c, (size_t)DM * D, dry); w.fc2_wTp16 = carve<uint16_t>(c, (size_t)DM * D, dry);
+            w.qkv_wT16 = bwd16_u16((size_t)3 * D * D); w.qkv_wTp16 = bwd16_u16((size_t)3 * D * D);
+            w.proj_wT16 = bwd16_u16((size_t)D * D); w.proj_wTp16 = bwd16_u16((size_t)D * D);
+            w.fc1_wT16 = bwd16_u16((size_t)DM * D); w.fc1_wTp16 = bwd16_u16((size_t)DM * D);
+            w.fc2_wT16 = bwd16_u16((size_t)DM * D); w.fc2_wTp16 = bwd16_u16((size_t)DM * D);
         }
     }
     if (bwd16) {
-        c->ad_up_wT16 = carve<uint16_t>(c, depth * RP * D, dry);
-        c->ad_down_wT16 = carve<uint16_t>(c, depth * RP * D, dry);
-        c->ad_scratch16 = carve<uint16_t>(c, 2 * depth * RP * D, dry);   // the two layouts of prep_adapters_kernel the backward does not read
+        c->ad_up_wT16 = bwd16_u16(depth * RP * D);
+        c->ad_down_wT16 = bwd16_u16(depth * RP * D);
+        c->ad_scratch16 = bwd16_u16(2 * depth * RP * D);   // the two layouts of prep_adapters_kernel the backward does not read
         c->ad_up_w3 = carve<uint16_t>(c, SA * depth * RP * D, dry);
     }
-    for (int sl = 0; sl < cf.slots; ++sl) {
+    for (int sl = 0; sl < (int)c->slots.size(); ++sl) {
         Slot& S = c->slots[sl];
         Transients& T = S.T;
         const size_t Mp = (M + 255) / 256 * 256;   // whole 256-row tiles: the fp8-correction kernel reads the rows of its last tile unclamped
@@ -525,19 +544,24 @@ static void layout_aux(dyt_ctx* c, bool dry, bool bwd16) {
         T.xn3 = carve<uint16_t>(c, Mp * SA * D, dry);
         T.g3 = carve<uint16_t>(c, Mp * SA * D, dry);
         T.h3 = carve<uint16_t>(c, Mp * SA * DM, dry);
-        T.dqkv3 = carve<uint16_t>(c, M * SA * 3 * D, dry);
+        T.dqkv3 = bwd16_u16(M * SA * 3 * D);
         if (!bwd16) continue;
         T.dact3 = carve<uint16_t>(c, Mp * SA * RP, dry);
         T.drop_src = carve<int>(c, M, dry);   // (ln_gather writes the dropped rows' list for their three-part up-projection launch)
-        T.dad16 = carve<uint16_t>(c, M * D, dry);
+        T.dad16 = bwd16_u16(M * D);
         T.qlo = carve<uint16_t>(c, M * D, dry); T.klo = carve<uint16_t>(c, M * D, dry); T.vlo = carve<uint16_t>(c, M * D, dry);
-        S.ucls16 = carve<uint16_t>(c, B * D, dry);
+        S.ucls16 = bwd16_u16(B * D);
         for (size_t l = 0; l < depth; ++l) {
             LayerS& L = S.L[l];
+            if (inf && l > 0) {   // the hi planes of q / k / v are the attention kernel's inputs; the rest exists for a saved pass (save16)
+                L.q16 = S.L[0].q16; L.k16 = S.L[0].k16; L.v16 = S.L[0].v16;
+                L.o16 = nullptr; L.ao3 = nullptr; L.u16 = nullptr; L.h16 = nullptr; L.z16 = nullptr; L.dact16 = nullptr;
+                continue;
+            }
             L.q16 = carve<uint16_t>(c, M * D, dry); L.k16 = carve<uint16_t>(c, M * D, dry); L.v16 = carve<uint16_t>(c, M * D, dry);
-            L.o16 = nullptr; L.ao3 = carve<uint16_t>(c, Mp * SA * D, dry);   // padded to whole 256-row tiles like the other fp8-form operand images (the 256x256 kernel reads its last tile unclamped)
-             L.u16 = carve<uint16_t>(c, M * D, dry); L.h16 = carve<uint16_t>(c, M * D, dry);
-            L.z16 = carve<uint16_t>(c, M * DM, dry); L.dact16 = carve<uint16_t>(c, M * RP, dry);
+            L.o16 = nullptr; L.ao3 = bwd16_u16(Mp * SA * D);   // padded to whole 256-row tiles like the other fp8-form operand images (the 256x256 kernel reads its last tile unclamped)
+             L.u16 = bwd16_u16(M * D); L.h16 = bwd16_u16(M * D);
+            L.z16 = bwd16_u16(M * DM); L.dact16 = bwd16_u16(M * RP);
         }
         if (!dry) S.u0_16_own = S.L[0].u16;
     }
@@ -605,7 +629,14 @@ static void trainable_layout(dyt_ctx* c) {
 }
 
 extern "C" const char* dyt_last_error(void) { return g_err; }
-extern "C" int dyt_version(void) { return 2; }   // 2: dyt_config::adapter_ln appended (round 6)
+extern "C" int dyt_version(void) { return 3; }   // 2: dyt_config::adapter_ln appended (round 6); 3: dyt_config::inference_only appended
+
+// dyt_config::inference_only: the entry points that need what such a context does not carve refuse before anything is enqueued
+static int refuse_inference(const dyt_ctx* c, const char* what) {
+    if (!c || !c->inf) return 0;
+    set_error("%s: the context was created with dyt_config.inference_only = 1 (eval forwards without DYT_F_SAVE only); create a training context for it", what);
+    return DYT_ERR_ARG;
+}
 // 16-bit operand type of this build: 0 = bfloat16 (libdyt_hip.so), 1 = IEEE half (libdyt_hip_f16.so)
 extern "C" int dyt_operand_type(void) {
 #ifdef DYT_FP16
@@ -635,8 +666,10 @@ extern "C" int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out) {
         set_error("adapter_ln=%d: 0 (none), 1 (in) or 2 (out); image model only", cfg->adapter_ln);
         return DYT_ERR_ARG;
     }
+    if (cfg->inference_only != 0 && cfg->inference_only != 1) { set_error("inference_only=%d: 0 or 1", cfg->inference_only); return DYT_ERR_ARG; }
     dyt_ctx* c = new dyt_ctx();
     c->cfg = *cfg;
+    c->inf = cfg->inference_only != 0;
     c->prec = cfg->precision;
     c->frames = cfg->frames > 1 ? cfg->frames : 1;
     c->ad_ln = cfg->adapter_ln;
@@ -780,19 +813,20 @@ static int refresh_split(dyt_ctx* c, int layer, hipStream_t s) {
     }
     if (layer < 0) return launch_split3_w((const float*)c->pe_w, c->pe_w3, D, D, s);
     LayerW& w = c->W[layer];
+    const bool t = !c->inf;   // the transposed images are the gradient GEMMs': an inference-only context has neither them nor their fp32 sources
     int rc = launch_split3_w((const float*)w.qkv_w, w.qkv_w3, 3 * D, D, s);
-    if (!rc) rc = launch_split3_w((const float*)w.qkv_wT, w.qkv_wT3, D, 3 * D, s);
+    if (!rc && t) rc = launch_split3_w((const float*)w.qkv_wT, w.qkv_wT3, D, 3 * D, s);
     if (!rc) rc = launch_split3_w((const float*)w.proj_w, w.proj_w3, D, D, s);
-    if (!rc) rc = launch_split3_w((const float*)w.proj_wT, w.proj_wT3, D, D, s);
+    if (!rc && t) rc = launch_split3_w((const float*)w.proj_wT, w.proj_wT3, D, D, s);
     if (!rc) rc = launch_split3_w((const float*)w.fc1_w, w.fc1_w3, DM, D, s);
-    if (!rc) rc = launch_split3_w((const float*)w.fc1_wT, w.fc1_wT3, D, DM, s);
+    if (!rc && t) rc = launch_split3_w((const float*)w.fc1_wT, w.fc1_wT3, D, DM, s);
     if (!rc) rc = launch_split3_w((const float*)w.fc2_w, w.fc2_w3, D, DM, s);
-    if (!rc) rc = launch_split3_w((const float*)w.fc2_wT, w.fc2_wT3, DM, D, s);
+    if (!rc && t) rc = launch_split3_w((const float*)w.fc2_wT, w.fc2_wT3, DM, D, s);
     return rc;
 }
 // bwd16: the 16-bit transposed copies (plain + MFMA fragment order) of one layer's matrices, from the fp32 transposed copies
 static int refresh_bwd16(dyt_ctx* c, int layer, hipStream_t s) {
-    if (c->prec != 0 || !c->bwd16 || layer < 0) return 0;
+    if (c->prec != 0 || !c->bwd16 || layer < 0 || c->inf) return 0;
     LayerW& w = c->W[layer];
     struct M16 { const void* src; void* dst; void* dstp; int N, K; };
     const M16 m[4] = {{w.qkv_wT, w.qkv_wT16, w.qkv_wTp16, D, 3 * D}, {w.proj_wT, w.proj_wT16, w.proj_wTp16, D, D},
@@ -994,19 +1028,22 @@ extern "C" int dyt_ctx_set_option(dyt_ctx* c, int option, int value) {
 extern "C" int dyt_set_drop_path(dyt_ctx* c, float rate) {
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
     if (!(rate >= 0.f) || rate >= 1.f) { set_error("drop_path rate %g out of [0, 1)", rate); return DYT_ERR_ARG; }
+    if (rate > 0.f) { int rc = refuse_inference(c, "dyt_set_drop_path"); if (rc) return rc; }   // (training passes only)
     c->drop_path_rate = rate;
     return DYT_OK;
 }
 extern "C" int dyt_set_drop_path_scales(dyt_ctx* c, int slot, const float* scales) {
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
     if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
-    c->slots[slot].dp_inject = scales;
+    if (scales) { int rc = refuse_inference(c, "dyt_set_drop_path_scales"); if (rc) return rc; }
+    c->slots[c->inf ? 0 : slot].dp_inject = scales;
     return DYT_OK;
 }
 
 extern "C" int dyt_set_soft_targets(dyt_ctx* c, const float* targets, int rows) {
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
     if (targets && rows < 1) { set_error("soft targets: rows = %d", rows); return DYT_ERR_ARG; }
+    if (targets) { int rc = refuse_inference(c, "dyt_set_soft_targets"); if (rc) return rc; }
     c->soft_targets = targets; c->soft_batch = targets ? rows : 0;
     return DYT_OK;
 }
@@ -1063,7 +1100,7 @@ static int prep_adapters(dyt_ctx* c, const float* trainable, hipStream_t s) {
     const bool out_ln = c->ad_ln == 2;
     float* up_bp = (c->learn_scale || out_ln) ? c->ad_up_bp : nullptr;
     const float ws_scale = out_ln ? c->cfg.adapter_scale : 0.f, b_scale = out_ln ? c->cfg.adapter_scale : 1.0f;
-    if (c->prec != 0 || c->bwd16)   // the 16-bit up_proj dgrad operand's power of two (read by prep_adapters_kernel<bf16> and the backward)
+    if ((c->prec != 0 || c->bwd16) && !c->inf)   // the 16-bit up_proj dgrad operand's power of two (read by prep_adapters_kernel<bf16> and the backward)
         hipLaunchKernelGGL(adapter_lift_kernel, dim3(c->cfg.depth), dim3(256), 0, s, trainable, c->layer_stride, c->off_uw, sc_off,
                            c->cfg.ffn_num, c->cfg.depth, c->ad_lift);
     if (c->prec == 0) {
@@ -1073,9 +1110,11 @@ static int prep_adapters(dyt_ctx* c, const float* trainable, hipStream_t s) {
                            (const float*)nullptr);
         if (c->bwd16) {   // + the 16-bit transposes the 16-bit backward's adapter dgrads multiply by
             bf16* scr = (bf16*)c->ad_scratch16;
+            if (!c->inf) {   // (an inference-only context has none of the four)
             hipLaunchKernelGGL(prep_adapters_kernel<bf16>, grid, dim3(256), 0, s, trainable, c->layer_stride, c->off_dw, c->off_db,
                                c->off_uw, c->cfg.ffn_num, scr, (bf16*)c->ad_down_wT16, scr + (size_t)c->cfg.depth * RP * D,
                                (bf16*)c->ad_up_wT16, c->ad_down_b, (bf16*)nullptr, 0.f, sc_off, c->off_ub, up_bp, b_scale, (const float*)c->ad_lift);
+            }
             if (c->ad_up_w3) {   // [hi | lo] image of the fp32 up-projection copies just written (all blocks: depth * 768 rows of 64)
                 int rc = launch_split3_w((const float*)c->ad_up_w, c->ad_up_w3, c->cfg.depth * D, RP, s);
                 if (rc) return rc;
@@ -1231,6 +1270,8 @@ static int forward_impl(dyt_ctx* c, int slot, const float* images, int B, int fl
     if (B < 1 || B > c->cfg.max_batch) { set_error("batch %d exceeds max_batch %d", B, c->cfg.max_batch); return DYT_ERR_ARG; }
     if (!images || !trainable || !logits) { set_error("null argument"); return DYT_ERR_ARG; }
     if ((g1 == nullptr) != (g2 == nullptr)) { set_error("g1 and g2 must be given together"); return DYT_ERR_ARG; }
+    if (flags & DYT_F_SAVE) { int rc = refuse_inference(c, slot > 0 ? "dyt_forward with DYT_F_SAVE into a slot > 0" : "dyt_forward with DYT_F_SAVE"); if (rc) return rc; }
+    if ((flags & DYT_F_TRAINING) && c->drop_path_rate > 0.f) { int rc = refuse_inference(c, "a training forward with stochastic depth"); if (rc) return rc; }
     const int P = c->prec, depth = c->cfg.depth, M = B * NT, r = c->cfg.ffn_num;
     const bool training = flags & DYT_F_TRAINING, complete = flags & DYT_F_COMPLETE, save = flags & DYT_F_SAVE;
     const bool masked_dense = (flags & DYT_F_MASKED_DENSE) && !complete;
@@ -1244,8 +1285,13 @@ static int forward_impl(dyt_ctx* c, int slot, const float* images, int B, int fl
     const bool planes = c->bwd16 && c->split16 && c->split_attn;   // q / k / v as 16-bit hi + lo planes (QKV epilogue -> split attention kernel; hi = what a 16-bit backward reads)
     const bool save16 = save && planes;   // "fp16x3h": what the backward reads is saved in the 16-bit operand type
     const bool fold = c->ln_fold && P != 0;   // LayerNorm-2 inside the fc1 GEMM (dyt_ctx::ln_fold)
-    Slot& S = c->slots[slot];
+    Slot& S = c->slots[c->inf ? 0 : slot];   // inference-only: one slot, whatever the index (it still seeds the pass's noise streams)
     Transients& T = S.T;
+    // inference-only: what an eval forward stores for the backward alone is not stored -- the launchers take a null pointer
+    // as "no-save variant"; values that flow on are computed by the same instructions
+    const bool nosave = c->inf;
+    // (the attention kernels with a no-save variant: the split fp32 kernel and the round-5 16-bit kernel; the other two keep their lse store)
+    const bool lse_nosave = nosave && (P == 0 ? (c->split16 && c->split_attn) : (get_attn_v2() & 1) != 0);
     S.valid = false;
     if (B % c->frames != 0) { set_error("video model: batch %d is not a multiple of frames %d", B, c->frames); return DYT_ERR_ARG; }
     if (do_prep) { int rc = prep_adapters(c, trainable, s); if (rc) return rc; rc = prep_pool(c, trainable, s); if (rc) return rc; }
@@ -1307,7 +1353,7 @@ static int forward_impl(dyt_ctx* c, int slot, const float* images, int B, int fl
             const bool tail_proj = c->cls_tail && l == depth - 1 && l > 0 && !tokens_out && !use_gate;
             AttnSave16 sv16{L.q16, L.k16, L.v16, nullptr};   // (the output's 16-bit copy is the hi plane of ao3)
             if (planes) { sv16.q_lo = T.qlo; sv16.k_lo = T.klo; sv16.v_lo = T.vlo; }   // bwd16: the 16-bit copies the backward reads (the fp32 output is then not needed once the proj operand is written)
-            RUN(1, 4.0 * B * NH * (double)NT * NT * HD, launch_attn_fwd(P, L.q, L.k, L.v, (save16 && ao3 && !tail_proj) ? nullptr : L.attn_o, L.lse, B, s, c->split16 && c->split_attn, ao3, (save16 || planes) ? &sv16 : nullptr, (fm >> 1) & 1, (planes && (fm & 32)) ? 1 : 3));
+            RUN(1, 4.0 * B * NH * (double)NT * NT * HD, launch_attn_fwd(P, L.q, L.k, L.v, (save16 && ao3 && !tail_proj) ? nullptr : L.attn_o, lse_nosave ? nullptr : L.lse, B, s, c->split16 && c->split_attn, ao3, (save16 || planes) ? &sv16 : nullptr, (fm >> 1) & 1, (planes && (fm & 32)) ? 1 : 3));
             if (tail_proj) {
                 // last block of a pass without a gate (teacher / complete model): only u[cls] is read downstream (LN2 / MLP / adapter of
                 // the cls rows, their backward) -- the proj GEMM runs on the B gathered cls rows; same k order, same bits for those rows
@@ -1458,6 +1504,7 @@ static int forward_impl(dyt_ctx* c, int slot, const float* images, int B, int fl
             }
             a.row_scale = dp2;
             if (tail) { a.splitk_ws = (float*)T.dZ; a.splitk_ws_bytes = (size_t)M * DM * c->at; }   // (a backward-pass buffer: idle here)
+            if (tail && c->inf) { a.splitk_ws = T.sk_ws; a.splitk_ws_bytes = (size_t)(DM / 256 + 1) * c->cfg.max_batch * D * sizeof(float); }   // (same decision in run_bf16: either size holds the B-row partials)
             RUN_GEMM(EPI_FC2, a);
         }
     }
@@ -1480,7 +1527,7 @@ extern "C" int dyt_forward(dyt_ctx* c, int slot, const float* images, int batch,
                            float* token_select, float* token_logits, void* stream) {
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
     if (slot >= 0 && slot < c->cfg.slots) {  // a stand-alone pass owns its block-0 buffers
-        Slot& S = c->slots[slot];
+        Slot& S = c->slots[c->inf ? 0 : slot];
         S.L[0].u = S.u0_own; S.L[0].u_at = S.u0_at_own; S.L[0].u16 = S.u0_16_own; S.L[0].ln_part = S.part0_own;
     }
     return forward_impl(c, slot, images, batch, flags, trainable, g1, g2, keep_mask, seed, logits, token_select,
@@ -1629,6 +1676,7 @@ static int dbg_poison(int bit, void* p, size_t bytes, hipStream_t s) {
 static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const float* dlogits, const float* dtoken_select,
                          const float* dtok, const float* dtoken_logits, float* grad, hipStream_t s,
                          hipEvent_t ev_split = nullptr, int split = 0) {
+    { int rc = refuse_inference(c, "the backward pass"); if (rc) return rc; }
     if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
     Slot& S = c->slots[slot];
     Transients& T = S.T;
@@ -1887,6 +1935,7 @@ static int backward_impl(dyt_ctx* c, int slot, const float* trainable, const flo
 extern "C" int dyt_backward(dyt_ctx* c, int slot, const float* dlogits, const float* dtoken_select, const float* dtok,
                             const float* dtoken_logits, float* grad_flat, void* stream) {
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
+    { int rc = refuse_inference(c, "dyt_backward"); if (rc) return rc; }
     if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
     return backward_impl(c, slot, c->slots[slot].trainable, dlogits, dtoken_select, dtok, dtoken_logits, grad_flat,
                          static_cast<hipStream_t>(stream));
@@ -1903,7 +1952,7 @@ extern "C" int dyt_loss(dyt_ctx* c, int slot_student, const float* logits_s, con
     if (slot_student < 0 || slot_student >= c->cfg.slots) { set_error("slot out of range"); return DYT_ERR_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     LossArgs a;
-    a.logits_s = logits_s; a.logits_t = logits_t; a.targets = targets; a.counts = c->slots[slot_student].counts;
+    a.logits_s = logits_s; a.logits_t = logits_t; a.targets = targets; a.counts = c->slots[c->inf ? 0 : slot_student].counts;
     a.batch = batch; a.C = c->cfg.num_classes; a.depth = c->cfg.depth;
     a.count_batch = batch * c->frames;   // video: `batch` clips, the gates were evaluated on batch * t frames
     a.target_ratio = token_target_ratio; a.loss_ratio = token_loss_ratio; a.token_minimal = token_minimal;
@@ -1943,6 +1992,7 @@ extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* 
                                 uint64_t seed, float token_target_ratio, float token_loss_ratio, float token_minimal,
                                 float token_minimal_weight, float* grad_flat, float* out_losses, float* logits_s,
                                 float* logits_t, float* token_select, void* stream) {
+    { int rc = refuse_inference(c, "dyt_step_fwd_bwd"); if (rc) return rc; }
     if (!c || !targets || !grad_flat || !out_losses) { set_error("null argument"); return DYT_ERR_ARG; }
     if (c->cfg.slots < 2) { set_error("dyt_step_fwd_bwd needs 2 slots"); return DYT_ERR_STATE; }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2096,6 +2146,7 @@ extern "C" int ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count,
 extern "C" const char* ncclGetErrorString(int result) __attribute__((weak));
 
 extern "C" int dyt_allreduce_grads(dyt_ctx* c, void* rccl_comm, float* grad_flat, void* comm_stream, void* stream) {
+    { int rc = refuse_inference(c, "dyt_allreduce_grads"); if (rc) return rc; }
     if (!c || !rccl_comm || !grad_flat) { set_error("null argument"); return DYT_ERR_ARG; }
     if (!ncclAllReduce) { set_error("RCCL is not loaded in this process (ncclAllReduce unresolved)"); return DYT_ERR_STATE; }
     constexpr int kNcclFloat32 = 7, kNcclSum = 0;
@@ -2123,6 +2174,7 @@ extern "C" int dyt_allreduce_grads(dyt_ctx* c, void* rccl_comm, float* grad_flat
 
 extern "C" int dyt_clip_grad_norm(dyt_ctx* c, float* grad, int64_t numel, float max_norm, float pre_scale, float* norm_out,
                                   void* stream) {
+    { int rc = refuse_inference(c, "dyt_clip_grad_norm"); if (rc) return rc; }
     if (!c || !grad || numel < 1 || !(max_norm > 0.f)) { set_error("bad argument"); return DYT_ERR_ARG; }
     return launch_clip_grad_norm(grad, numel, max_norm, pre_scale, c->clip_scratch, norm_out, static_cast<hipStream_t>(stream));
 }
@@ -2130,6 +2182,7 @@ extern "C" int dyt_clip_grad_norm(dyt_ctx* c, float* grad, int64_t numel, float 
 extern "C" int dyt_debug_dispatch(dyt_ctx* c, int slot, int layer, int32_t* row_src, int32_t* dst_of, int32_t* counts,
                                   int32_t* total, void* stream) {
     if (!c || slot < 0 || slot >= c->cfg.slots || layer < 0 || layer >= c->cfg.depth) { set_error("bad slot / layer"); return DYT_ERR_ARG; }
+    { int rc = refuse_inference(c, "dyt_debug_dispatch (per-block index arrays of a pass)"); if (rc) return rc; }
     const Slot& S = c->slots[slot];
     if (S.batch < 1) { set_error("slot %d holds no pass", slot); return DYT_ERR_STATE; }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2146,6 +2199,7 @@ extern "C" int dyt_debug_dispatch(dyt_ctx* c, int slot, int layer, int32_t* row_
 // or B for the last block in the cls-only tail form.  Test accessor (tests/parity_rules.py checks which side of the ReLU a unit is on).
 extern "C" int dyt_debug_dact(dyt_ctx* c, int slot, int layer, float* out, int* rows_out, void* stream) {
     if (!c || !out || slot < 0 || slot >= c->cfg.slots || layer < 0 || layer >= c->cfg.depth) { set_error("bad slot / layer"); return DYT_ERR_ARG; }
+    { int rc = refuse_inference(c, "dyt_debug_dact (per-block tensors of a saved pass)"); if (rc) return rc; }
     const Slot& S = c->slots[slot];
     if (S.batch < 1) { set_error("slot %d holds no pass", slot); return DYT_ERR_STATE; }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2162,6 +2216,7 @@ extern "C" int dyt_debug_dact(dyt_ctx* c, int slot, int layer, float* out, int* 
 
 extern "C" int dyt_debug_drop_path(dyt_ctx* c, int slot, float* out, void* stream) {
     if (!c || !out || slot < 0 || slot >= c->cfg.slots) { set_error("bad slot"); return DYT_ERR_ARG; }
+    { int rc = refuse_inference(c, "dyt_debug_drop_path"); if (rc) return rc; }
     const Slot& S = c->slots[slot];
     if (S.batch < 1 || !S.dp) { set_error("slot %d: the last pass ran without stochastic depth", slot); return DYT_ERR_STATE; }
     DYT_HIP_CHECK(hipMemcpyAsync(out, S.dp, (size_t)2 * c->cfg.depth * S.batch * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
@@ -2493,6 +2548,7 @@ extern "C" int dyt_mlp_gathered_fwd(dyt_ctx* c, int layer, const float* u, const
 extern "C" int dyt_mlp_gathered_bwd(dyt_ctx* c, int layer, const float* u, const float* mask, const float* dy, float* du, int batch,
                                     void* stream) {
     if (!c || !u || !mask || !dy || !du || layer < 0 || layer >= c->cfg.depth || batch < 1 || batch > c->cfg.max_batch) { set_error("bad argument"); return DYT_ERR_ARG; }
+    { int rc = refuse_inference(c, "dyt_mlp_gathered_bwd"); if (rc) return rc; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = c->prec, M = batch * NT;
     const float gs = P == 0 ? 1.0f : c->gs;

@@ -281,9 +281,11 @@ def as_fused(optimizer, model):
     ``lr_sched.adjust_learning_rate`` and any later edit reach the kernel), state it may hold from ``misc.load_model`` is taken
     over, and from then on its ``state`` aliases the fused moments -- no driver line changes.  Anything the flat AdamW kernel
     does not implement raises."""
+    m = getattr(model, "module", model)
+    if getattr(m, "inference_only", False):
+        raise DyTError("as_fused: the model was built with inference_only (eval forwards only); build it without inference_only to train")
     if isinstance(optimizer, FusedAdamW):
         return optimizer
-    m = getattr(model, "module", model)
     fused = getattr(optimizer, "_dyt_fused", None)
     if fused is not None and fused.model is m:
         return fused
@@ -392,6 +394,8 @@ def train_step(model, samples, targets, optimizer, criterion=None, losses_out=No
     ``targets``: integer labels [b], or class probabilities [b, num_classes] (a ``mixup_fn``'s output, reference :44-45) -- both
     CrossEntropyLoss terms then take the soft form (C ABI dyt_set_soft_targets)."""
     m = getattr(model, "module", model)
+    if getattr(m, "inference_only", False):
+        raise DyTError("train_step: the model was built with inference_only (eval forwards only); build it without inference_only to train")
     samples = m.fold_input(samples.float()).contiguous()   # video: [b,c,t,h,w] -> [(b t),c,h,w]
     eng = m.engine(samples.shape[0], samples.device)
     # nn.CrossEntropyLoss(label_smoothing = e) is the soft form with t (1 - e) + e / C (torch applies the same map to class-probability targets)

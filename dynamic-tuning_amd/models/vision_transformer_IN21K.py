@@ -13,7 +13,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from _lib import DyTError, OPT_COUNT_FLOPS_TOKENS, key_to_param, is_trainable_param
+from _lib import DyTError, OPT_COUNT_FLOPS_TOKENS, inference_only_default, key_to_param, is_trainable_param
 from runtime import DyTEngine, parse_precision
 from .dynamic_adapter import Adapter, TokenSelect, _LinearParams
 
@@ -189,7 +189,7 @@ class VisionTransformer(nn.Module):
                  no_embed_class=False, pre_norm=False, fc_norm=None, drop_rate=0., pos_drop_rate=0., patch_drop_rate=0.,
                  proj_drop_rate=0., attn_drop_rate=0., drop_path_rate=0., weight_init='', embed_layer=None,
                  norm_layer=None, act_layer=None, block_fn=Block, mlp_layer=None, tuning_config=None, select_config=None,
-                 precision=None, max_batch=None, train_mode=None):
+                 precision=None, max_batch=None, train_mode=None, inference_only=None):
         super().__init__()
         fixed = dict(img_size=(img_size, 224), patch_size=(patch_size, 16), in_chans=(in_chans, 3), embed_dim=(embed_dim, 768),
                      num_heads=(num_heads, 12), mlp_ratio=(mlp_ratio, 4.0), qkv_bias=(qkv_bias, True), global_pool=(global_pool, 'token'),
@@ -238,6 +238,10 @@ class VisionTransformer(nn.Module):
         self.train_mode = train_mode or _cfg_get(tuning_config, "dyt_train_mode") or os.environ.get("DYT_TRAIN_MODE", "masked")
         assert self.train_mode in ("compact", "masked")
         self.max_batch = max_batch
+        # inference_only (keyword, else tuning_config.dyt_inference_only, else env DYT_INFERENCE_ONLY, else off): the library context is laid out
+        # for eval forwards alone (dyt_config.inference_only: a fraction of the training arena, any batch size that fits); train() mode, a
+        # forward that would record a graph, train_step and as_fused raise DyTError
+        self.inference_only = inference_only_default(inference_only, tuning_config)
         self._engine = None
         self._sync_state = None
         self._seed_counter = 0
@@ -281,10 +285,10 @@ class VisionTransformer(nn.Module):
                             precision=self.precision, max_batch=mb, depth=self.depth,
                             adapter_dropout=self.blocks[0].adaptmlp.dropout, tau=self.blocks[0].mlp_token_select.tau,
                             threshold=self.blocks[0].mlp_token_select.threshold, frames=self._frames or 1,
-                            adapter_ln=self.blocks[0].adaptmlp.adapter_ln_code)
+                            adapter_ln=self.blocks[0].adaptmlp.adapter_ln_code, inference=self.inference_only)
             self._engine = eng
             self._sync_state = None
-        if getattr(eng, "drop_path_rate", 0.0) != self.drop_path_rate:
+        if not self.inference_only and getattr(eng, "drop_path_rate", 0.0) != self.drop_path_rate:   # (stochastic depth: training passes only)
             eng.set_drop_path(self.drop_path_rate)
         self._sync(eng)
         return eng
@@ -309,6 +313,18 @@ class VisionTransformer(nn.Module):
                 p.data = view
             self._trainables.append((n, p))
 
+    def _refuse_training(self, what, grad_check=True):
+        """An inference_only model refuses, before any library call, what its context has no buffers for."""
+        if not self.inference_only:
+            return
+        if self.training:
+            raise DyTError("%s: the model was built with inference_only (eval forwards only) and is in train() mode; call .eval(), or "
+                           "build it without inference_only to train" % what)
+        if grad_check and torch.is_grad_enabled() and any(p.requires_grad for n, p in self.named_parameters()
+                                                          if is_trainable_param(key_to_param(n)[0])):
+            raise DyTError("%s with grad enabled: the model was built with inference_only and saves nothing for a backward pass; call it "
+                           "under torch.no_grad() (or requires_grad_(False)), or build it without inference_only" % what)
+
     # ---- reference API ------------------------------------------------------------------------
     def forward(self, x, complete_model=False, gumbel=None, keep_mask=None):
         """x [B,3,224,224] -> (logits [B,C], {"token_select": [B,12,196,1], "token_logits": [B,12,196,1]}).
@@ -318,6 +334,7 @@ class VisionTransformer(nn.Module):
         stream seeded from torch's seed and a per-model call counter."""
         if not x.is_cuda:
             raise DyTError("DyT VisionTransformer runs on a HIP device only (input is on %s); there is no CPU path" % x.device)
+        self._refuse_training("forward")
         x = self.fold_input(x.float()).contiguous()
         eng = self.engine(x.shape[0], x.device)
         # FLOP-probe variant (reference Block.forward_count_flops :167-185, set through
@@ -358,6 +375,7 @@ class VisionTransformer(nn.Module):
             raise DyTError("DyT VisionTransformer runs on a HIP device only (input is on %s); there is no CPU path" % x.device)
         if self._frames and self._frames > 1:
             raise NotImplementedError("forward_features of the video model: its head pools every frame's tokens inside the fused forward")
+        self._refuse_training("forward_features", grad_check=False)
         x = self.fold_input(x.float()).contiguous()
         eng = self.engine(x.shape[0], x.device)
         g1 = g2 = None

@@ -41,7 +41,7 @@ def parse_precision(p):
 
 class DyTEngine:
     def __init__(self, num_classes, ffn_num, adapter_scale, device, precision=PREC_BF16, max_batch=128, depth=12,
-                 slots=2, adapter_dropout=0.1, tau=5.0, threshold=0.5, frames=1, adapter_ln=0):
+                 slots=2, adapter_dropout=0.1, tau=5.0, threshold=0.5, frames=1, adapter_ln=0, inference=False):
         if torch.device(device).type != "cuda":
             raise DyTError("the DyT path runs on a HIP device only (got %s); there is no CPU path" % (device,))
         self.device = torch.device(device)
@@ -58,7 +58,11 @@ class DyTEngine:
         self.learnable_scale = isinstance(adapter_scale, torch.Tensor)
         self.cfg = Config(int(num_classes), int(ffn_num), int(depth), lib_prec,
                           int(max_batch), int(slots), 1.0 if self.learnable_scale else float(adapter_scale), float(adapter_dropout), float(tau),
-                          float(threshold), int(frames), int(adapter_ln))   # adapter_ln: 0 none / 1 "in" / 2 "out" (tuning_config.ffn_adapter_layernorm_option)
+                          float(threshold), int(frames), int(adapter_ln),   # adapter_ln: 0 none / 1 "in" / 2 "out" (tuning_config.ffn_adapter_layernorm_option)
+                          1 if inference else 0)
+        # inference=True (dyt_config.inference_only): a context for eval forwards alone -- one set of per-block buffers, one slot, no backward
+        # transients, no dgrad weight images; everything that trains raises DyTError (here for the entries that take no context, else in the library)
+        self.inference = bool(inference)
         self.adapter_ln = int(adapter_ln)
         self.frames = max(1, int(frames))   # > 1: video model, every batch is clips * frames images
         self.L = lib(fp16=self.precision == PREC_FP16 or split != 0)
@@ -81,7 +85,7 @@ class DyTEngine:
             for layer in range(int(depth)):
                 self._ck(self.L.dyt_trainable_offset(self.h, P_AD_SCALE, layer, ctypes.byref(off), ctypes.byref(num)))
                 self.flat[off.value:off.value + num.value] = 1.0
-        self.grad = torch.zeros_like(self.flat)
+        self.grad = None if self.inference else torch.zeros_like(self.flat)   # (no gradient buffer beside an inference-only context)
         self.losses = torch.zeros(8, device=self.device, dtype=torch.float32)
         self._graphs = {}          # captured hipGraphs of the step, keyed by its static arguments
         self._comm_stream = None   # side stream of the early (upper-half) gradient all-reduce
@@ -93,6 +97,13 @@ class DyTEngine:
 
     def _ck(self, rc):
         check(rc, self.L)
+
+    def _refuse_inference(self, what):
+        """For the entries the library cannot refuse itself (dyt_adamw* take no context) or that do host-side work first; every other
+        training entry is refused by the library (DYT_ERR_ARG, the text names inference_only) before it enqueues anything."""
+        if self.inference:
+            raise DyTError("%s: this engine holds an inference_only context (eval forwards only); build the model / engine without "
+                           "inference_only to train" % what)
 
     def __del__(self):
         try:
@@ -242,6 +253,7 @@ class DyTEngine:
         cost per step drops from ~13 ms to well under 1 ms, which is what keeps 8 ranks on a 16-core host from
         becoming launch-bound).  Inputs are copied into static device buffers; the Philox seed lives on the device
         (DYT_F_DEVICE_SEED) and is set from `seed` before every replay, exactly the value an eager step with the same `seed` uses."""
+        self._refuse_inference("step_graph")
         key = (tuple(images.shape), tuple(targets.shape), float(target_ratio), float(loss_ratio), float(token_minimal),
                float(token_minimal_weight), bool(masked_dense), bool(accumulate))
         ent = self._graphs.get(key)
@@ -291,6 +303,7 @@ class DyTEngine:
     def adamw(self, exp_avg, exp_avg_sq, step, lr, weight_decay=0.01, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
         """torch.optim.AdamW semantics over the flat buffer (main_image.py:285); the moments belong to the optimizer
         object (engine_finetune.FusedAdamW) and survive a re-created engine; `step` is the 1-based update count."""
+        self._refuse_inference("adamw")   # (dyt_adamw takes no context: the refusal of an inference_only engine is made here)
         with torch.cuda.device(self.device):
             self._ck(self.L.dyt_adamw(ptr(self.flat), ptr(self.grad), ptr(exp_avg), ptr(exp_avg_sq), self.n_train,
                                    int(step), lr, beta1, beta2, eps, weight_decay, grad_scale, stream_ptr()))
@@ -298,6 +311,7 @@ class DyTEngine:
     def adamw_guarded(self, exp_avg, exp_avg_sq, state, lr, weight_decay=0.01, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
         """The same update, skipped (and counted in `state`, a device int32[4]) when the gradient holds inf / NaN: GradScaler.step
         semantics (misc.py:256-272) without a host sync; the step count of the bias corrections lives in state[0]."""
+        self._refuse_inference("adamw_guarded")
         with torch.cuda.device(self.device):
             self._ck(self.L.dyt_adamw_guarded(ptr(self.flat), ptr(self.grad), ptr(exp_avg), ptr(exp_avg_sq), self.n_train, ptr(state),
                                            lr, beta1, beta2, eps, weight_decay, grad_scale, stream_ptr()))
@@ -414,6 +428,7 @@ class DyTEngine:
     def allreduce_native(self, overlap=True):
         """dyt_allreduce_grads: SUM of the flat gradient over the ranks on the library's own RCCL communicator (created on
         first use over the default torch.distributed group); the upper part on the communication stream when `overlap`."""
+        self._refuse_inference("allreduce_native")
         if self._rccl_comm is None:
             from _lib import rccl_comm_shared
             self._rccl_comm = rccl_comm_shared(self.device)   # one communicator per process and device, shared by every engine

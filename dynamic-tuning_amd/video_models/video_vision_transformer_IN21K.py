@@ -50,8 +50,8 @@ class AttentiveBlock(nn.Module):
 class VisionTransformer(_ImageViT):
     """Reference :282-483."""
 
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
+    def __init__(self, *args, inference_only=None, **kwargs):
+        super().__init__(*args, inference_only=inference_only, **kwargs)
         self.query_token = nn.Parameter(torch.zeros(1, 1, self.embed_dim))          # :407
         self.attentive_blocks = AttentiveBlock(self.embed_dim, 12, qkv_bias=True)   # :408-410
         self.attentive_blocks.apply(self.init_weights)

@@ -125,6 +125,16 @@ typedef struct dyt_config {
                                 the scaled adapter output goes through that LayerNorm before it joins the residual stream.  Adds the two
                                 [768] tensors DYT_P_AD_LN_W / _B per block to the flat trainable layout.  Generic row kernels (no fusion, no
                                 cls-only tail); image model only.  (ABI v2: the field was appended in round 6.) */
+    int32_t inference_only;  /* 0: the training layout (every pass kind, two slots of saved activations, the backward's transients and weight
+                                images).  1: a context for eval forwards alone -- ONE set of per-block buffers shared by all `depth` blocks, one
+                                slot (every slot index runs in it), two residual streams used in turn, the forward's transients, and none of the
+                                transposed / fragment-order weight images only the gradient GEMMs read.  Results are bit-identical to the same
+                                eval forward in a training-layout context.  dyt_forward with DYT_F_SAVE, dyt_backward, dyt_step_fwd_bwd,
+                                dyt_allreduce_grads, dyt_clip_grad_norm, dyt_set_soft_targets, dyt_set_drop_path(_scales) with a non-zero
+                                argument, dyt_mlp_gathered_bwd and the saved-pass accessors (dyt_debug_dispatch / _dact / _drop_path) return
+                                DYT_ERR_ARG (the text names inference_only) before anything is enqueued.  dyt_adamw* take no context: their
+                                caller refuses (runtime.DyTEngine).
+                                (ABI v3: appended last.) */
 } dyt_config;
 
 typedef struct dyt_ctx dyt_ctx;
