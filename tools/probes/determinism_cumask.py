@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "dynamic-tuning_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 mask = os.environ.get("PMASK", "none")
 if mask != "none":
-    os.environ["DYT_DBG_SIDE_CU_MASK"] = mask   # cu | xcd | iso (with DYT_DBG_ISO=<class bits>, see csrc/model.hip)
+    os.environ["DYT_DBG_SIDE_CU_MASK"] = mask   # cu | xcd | iso (with DYT_DBG_ISO=<class bits>, see csrc/debug.hip)
 import torch
 import _lib, synth
 if os.environ.get("DYT_LIB_PATH"):   # A/B against another build of the library

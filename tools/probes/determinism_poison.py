@@ -1,4 +1,4 @@
-"""Stale-read detector: backward transients are filled with NaN patterns right before their producer kernels (DYT_DBG_POISON, csrc/model.hip);
+"""Stale-read detector: backward transients are filled with NaN patterns right before their producer kernels (DYT_DBG_POISON, csrc/debug.hip);
 a consumer that reads a row its producer has not made visible yet turns the gradient into NaN.  PPOISON=<mask> PB=128 PRUNS=6"""
 import os, sys
 os.environ["DYT_DBG_POISON"] = os.environ.get("PPOISON", "511")

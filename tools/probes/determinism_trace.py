@@ -1,5 +1,5 @@
 """Locates the first backward kernel launch whose output differs between two runs of the same step (DYT_DBG_CKSUM hook of
-csrc/model.hip: an integer checksum of every backward launch's output, per pass, in launch order).
+csrc/debug.hip: an integer checksum of every backward launch's output, per pass, in launch order).
 PB=128 PRUNS=5 python tools/probes/determinism_trace.py"""
 import ctypes, os, sys
 os.environ["DYT_DBG_CKSUM"] = "1"
