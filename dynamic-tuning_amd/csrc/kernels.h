@@ -239,7 +239,7 @@ int launch_seed_advance(uint64_t* seed_dev, hipStream_t s);
 // then g *= min(1, max_norm / (norm + 1e-6)); scratch: 256 floats
 int launch_clip_grad_norm(float* g, int64_t n, float max_norm, float pre_scale, float* scratch, float* norm_out, hipStream_t s);
 int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
-                 float eps, float wd, float bc1, float bc2, float gscale, hipStream_t s);
+                 float eps, float wd, float bc1, float rsqrt_bc2, float gscale, hipStream_t s);   // bias corrections: formed in double by the caller
 
 // ... guarded: skipped (and counted) when the gradient holds inf / NaN; state = device int[4] {applied, skipped, flag, -}; bias corrections
 // from the device-side applied count

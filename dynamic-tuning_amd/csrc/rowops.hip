@@ -744,7 +744,9 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a, float* __res
     ms = wave_max(ms); mt = wave_max(mt);
     float ss = 0.f, st = 0.f;
     for (int c = lane; c < C; c += 64) { ss += expf(ls[c] - ms); st += expf(lt[c] - mt); }
-    const float lse_s = ms + logf(wave_sum(ss)), lse_t = mt + logf(wave_sum(st));
+    // log p = (logit - max) - log(sum): the row maximum is never added to the O(1) log-sum, so a common shift of the logits (1e4, say)
+    // does not round log p to an ulp of the shift
+    const float lgs_s = logf(wave_sum(ss)), lgs_t = logf(wave_sum(st));
     if (a.soft) {   // class-probability targets (LossArgs::soft): same form with the one-hot row replaced by t
         const float* tg = a.soft + (size_t)b * C;
         float tsum = 0.f;
@@ -752,7 +754,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a, float* __res
         tsum = wave_sum(tsum);
         float klb = 0.f, ces = 0.f, cet = 0.f;
         for (int c = lane; c < C; c += 64) {
-            const float lps = ls[c] - lse_s, lpt = lt[c] - lse_t;
+            const float lps = (ls[c] - ms) - lgs_s, lpt = (lt[c] - mt) - lgs_t;
             const float ps = expf(lps), pt = expf(lpt), t = tg[c];
             klb += pt * (lpt - lps);
             ces -= t * lps; cet -= t * lpt;
@@ -766,7 +768,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a, float* __res
     const int y = (int)a.targets[b];
     float klb = 0.f;
     for (int c = lane; c < C; c += 64) {
-        const float lps = ls[c] - lse_s, lpt = lt[c] - lse_t;
+        const float lps = (ls[c] - ms) - lgs_s, lpt = (lt[c] - mt) - lgs_t;
         const float ps = expf(lps), pt = expf(lpt);
         klb += pt * (lpt - lps);
         const float oh = c == y ? 1.0f : 0.0f;
@@ -775,8 +777,8 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a, float* __res
     }
     klb = wave_sum(klb);
     if (lane == 0) {
-        part[b * 4 + 0] = -(ls[y] - lse_s);
-        part[b * 4 + 1] = -(lt[y] - lse_t);
+        part[b * 4 + 0] = -((ls[y] - ms) - lgs_s);
+        part[b * 4 + 1] = -((lt[y] - mt) - lgs_t);
         part[b * 4 + 2] = klb;
     }
 }
@@ -809,8 +811,9 @@ __global__ __launch_bounds__(256) void loss_final_kernel(LossArgs a, const float
             d0 = a.loss_ratio * 2.0f * diff / N;
             if (a.token_minimal_weight > 0.f) {
                 tok += a.token_minimal_weight * ((N - keptv) * fmaxf(a.token_minimal, 0.f) + keptv * fmaxf(a.token_minimal - 1.0f, 0.f));
-                d1 = a.token_minimal > 0.f ? -a.loss_ratio * a.token_minimal_weight : 0.f;
-                d2 = a.token_minimal > 1.f ? -a.loss_ratio * a.token_minimal_weight : 0.f;
+                // clamp(min=0)'s backward passes the gradient AT the bound too (autograd: x >= min), so token_minimal == 0 / == 1 count
+                d1 = a.token_minimal >= 0.f ? -a.loss_ratio * a.token_minimal_weight : 0.f;
+                d2 = a.token_minimal >= 1.f ? -a.loss_ratio * a.token_minimal_weight : 0.f;
             }
         }
         const float token_loss = a.loss_ratio * tok;
@@ -859,13 +862,21 @@ __global__ __launch_bounds__(256) void grad_nonfinite_kernel(const float* __rest
     }
     if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(state + 2, 1);
 }
-__global__ void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                      float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                                      float gscale, const int* __restrict__ state) {
+    // bias corrections in double, once per workgroup, rounded to fp32 exactly as dyt_adamw's host code hands them to adamw_kernel
+    // (1 - powf(0.999f, step) in fp32 is up to 7e-6 relative off in the first steps: the whole update of a zero-initialised parameter)
+    __shared__ float bc_s[2];
+    if (threadIdx.x == 0) {
+        const double step = (double)(state[0] + 1);
+        bc_s[0] = (float)(1.0 - pow((double)b1, step));
+        bc_s[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+    }
+    __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || state[2] != 0) return;   // non-finite gradient somewhere: parameters and moments stay as they are
-    const float step = (float)(state[0] + 1);
-    const float bc1 = 1.0f - powf(b1, step), rsqrt_bc2 = 1.0f / sqrtf(1.0f - powf(b2, step));
+    const float bc1 = bc_s[0], rsqrt_bc2 = bc_s[1];
     const float gi = g[i] * gscale;
     float pi = p[i] * (1.0f - lr * wd);
     const float mi = b1 * m[i] + (1.0f - b1) * gi;
@@ -937,9 +948,9 @@ int launch_clip_grad_norm(float* g, int64_t n, float max_norm, float pre_scale, 
 }
 
 int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                 float wd, float bc1, float bc2, float gscale, hipStream_t s) {
+                 float wd, float bc1, float rsqrt_bc2, float gscale, hipStream_t s) {
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps,
-                       wd, bc1, 1.0f / sqrtf(bc2), gscale);
+                       wd, bc1, rsqrt_bc2, gscale);
     LAUNCH_CHECK();
     return 0;
 }

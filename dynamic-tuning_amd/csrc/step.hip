@@ -31,8 +31,11 @@ extern "C" int dyt_adamw(float* param, const float* grad, float* exp_avg, float*
                          float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                          void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || numel < 1 || step < 1) { set_error("bad argument"); return DYT_ERR_ARG; }
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    return launch_adamw(param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,
+    // bias corrections in double (as torch.optim.AdamW forms them), handed to the kernel as floats: 1 - powf(0.999f, step) in fp32 is
+    // up to 7e-6 relative off in the first steps, which is the whole update of a parameter that starts at zero
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+    return launch_adamw(param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, bc1, rsqrt_bc2, grad_scale,
                         static_cast<hipStream_t>(stream));
 }
 
