@@ -25,6 +25,7 @@ PREC_FP16F8 = 6   # host-side name only: PREC_FP16X3H with the forward GEMMs' co
 PREC_FP16X3Q = 7  # host-side name only: PREC_FP16X3H with the attention branch's GEMMs (qkv, proj) in the fp8-correction form, the MLP three-part (DYT_OPT_F32_SPLIT16 = 5)
 PREC_FP16X3 = 3   # host-side name only: libdyt_hip_f16.so in its fp32 mode with DYT_OPT_F32_SPLIT16 (frozen-weight GEMMs as three IEEE-half products)
 F_TRAINING, F_COMPLETE, F_SAVE, F_MASKED_DENSE, F_GATE_ALWAYS, F_ACCUM_GRAD, F_DEVICE_SEED, F_TOKENS_IN, F_TOKENS_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256
+CREATE_WIDE_HEAD = 1   # dyt_ctx_create_ex: DYT_CREATE_WIDE_HEAD (the head on the MFMA kernels of csrc/head_wide.hip, up to 65 536 classes)
 OPT_STREAM_OVERLAP, OPT_CLS_TAIL, OPT_SHARE_BLOCK0, OPT_COUNT_FLOPS_TOKENS, OPT_GRAD_SCALE_LOG2, OPT_FC2_CAT, OPT_ATTN_BWD_FUSED, OPT_F32_SPLIT16, OPT_ATTN_V2, OPT_GEMM_SPLITK, OPT_LEARNABLE_SCALE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 
 # enum dyt_param (include/dyt_hip.h)
@@ -105,6 +106,23 @@ def inference_only_default(explicit=None, tuning_config=None):
     return os.environ.get("DYT_INFERENCE_ONLY", "0").strip().lower() not in ("", "0", "false", "no", "off")
 
 
+def wide_head_default(explicit=None, tuning_config=None, num_classes=0):
+    """The image models' ``wide_head`` keyword: the explicit value, else ``tuning_config.dyt_wide_head``, else the environment's
+    DYT_WIDE_HEAD, else ``num_classes > 1024`` (what the row-kernel head refuses)."""
+    if explicit is not None:
+        return bool(explicit)
+    try:
+        v = getattr(tuning_config, "dyt_wide_head")
+    except (AttributeError, KeyError):
+        v = None
+    if v is not None:
+        return bool(v)
+    e = os.environ.get("DYT_WIDE_HEAD")
+    if e is not None and e.strip() != "":
+        return e.strip().lower() not in ("0", "false", "no", "off")
+    return int(num_classes) > 1024
+
+
 _lib = None
 
 _vp, _i, _i64, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
@@ -115,6 +133,7 @@ SYMBOLS = {
     "dyt_version": (_i, []),
     "dyt_operand_type": (_i, []),
     "dyt_ctx_create": (_i, [ctypes.POINTER(Config), ctypes.POINTER(_vp)]),
+    "dyt_ctx_create_ex": (_i, [ctypes.POINTER(Config), ctypes.c_uint32, ctypes.POINTER(_vp)]),
     "dyt_ctx_destroy": (_i, [_vp]),
     "dyt_ctx_bytes": (_i, [_vp, ctypes.POINTER(_i64)]),
     "dyt_ctx_set_option": (_i, [_vp, _i, _i]),
@@ -146,6 +165,7 @@ SYMBOLS = {
     "dyt_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "dyt_adapter_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _u64, _i, _vp]),
     "dyt_adapter_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _u64, _i, _vp]),
+    "dyt_head_wide": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "dyt_mlp_gathered_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "dyt_mlp_gathered_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "dyt_gate_compact": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

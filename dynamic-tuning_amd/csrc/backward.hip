@@ -139,6 +139,11 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
         int rc = pool_backward(c, S, trainable, dlogits, grad, s);
         if (rc) return rc;
     } else {
+        if (c->wide_head)
+            RUN(2, 0, launch_head_wide_bwd(dlogits, S.xs[depth], (size_t)NT * D, S.cls_n, S.head_stats, c->norm_w, trainable + c->off_hw,
+                                           cls_tail ? S.gcls : g, grad + c->off_hw, grad + c->off_hb, B, c->cfg.num_classes,
+                                           cls_tail ? 1 : 0, S.head_part, s));
+        else
         RUN(2, 0, launch_head_bwd(dlogits, S.xs[depth], S.cls_n, S.head_stats, c->norm_w, trainable + c->off_hw,
                                   cls_tail ? S.gcls : g, grad + c->off_hw, grad + c->off_hb, B, c->cfg.num_classes,
                                   cls_tail ? 1 : 0, s));

@@ -104,6 +104,7 @@ struct Slot {
     float* gcls = nullptr;   // last block backward: gradient at the cls rows [B,768]
     float* cls_n = nullptr;
     float2* head_stats = nullptr;
+    float* head_part = nullptr;   // dyt_ctx::wide_head, training layout: [ceil(C/1024)][max_batch][768] class-slice partial sums of the head's dx (per slot: the two passes' backward run on two streams)
     int batch = 0, flags = 0;
     bool valid = false;
     bool saved16 = false;    // the saved pass holds the 16-bit tensors of a 16-bit backward (dyt_ctx::bwd16)
@@ -120,6 +121,9 @@ struct dyt_ctx {
     // dyt_config::inference_only: one aliased LayerS, one slot, two residual streams, forward transients and forward weight images only
     // (layout / layout_aux); every entry point that needs more refuses (refuse_inference)
     bool inf = false;
+    // DYT_CREATE_WIDE_HEAD (dyt_ctx_create_ex): the head runs on the MFMA kernels of head_wide.hip (num_classes up to 65 536) instead of the row
+    // kernels of rowops.hip (up to 1024, the bit-pinned default); image model only
+    bool wide_head = false;
     int prec;
     size_t at;  // bytes per activation element
     char* arena = nullptr;

@@ -88,6 +88,7 @@ static void layout(dyt_ctx* c, bool dry) {
         S.gcls = bwd_f32(B * D);
         S.cls_n = carve<float>(c, B * D, dry);
         S.head_stats = carve<float2>(c, B, dry);
+        if (c->wide_head) S.head_part = bwd_f32(head_wide_scratch_floats((int)B, (int)C));
         for (size_t l = 0; l < depth; ++l) {
             LayerS& L = S.L[l];
             if (inf && l > 0) { L = S.L[0]; continue; }   // one set of per-block buffers: every block's launches run in stream order, each rewrites what it reads
@@ -308,7 +309,7 @@ static void trainable_layout(dyt_ctx* c) {
 }
 
 extern "C" const char* dyt_last_error(void) { return g_err; }
-extern "C" int dyt_version(void) { return 3; }   // 2: dyt_config::adapter_ln appended (round 6); 3: dyt_config::inference_only appended
+extern "C" int dyt_version(void) { return 4; }   // 2: dyt_config::adapter_ln appended (round 6); 3: dyt_config::inference_only appended; 4: dyt_ctx_create_ex, dyt_head_wide
 
 // dyt_config::inference_only: the entry points that need what such a context does not carve refuse before anything is enqueued
 int dyt::refuse_inference(const dyt_ctx* c, const char* what) {
@@ -325,13 +326,22 @@ extern "C" int dyt_operand_type(void) {
 #endif
 }
 
-extern "C" int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out) {
+extern "C" int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out) { return dyt_ctx_create_ex(cfg, 0, out); }
+
+extern "C" int dyt_ctx_create_ex(const dyt_config* cfg, uint32_t create_flags, dyt_ctx** out) {
     if (!cfg || !out) { set_error("null argument"); return DYT_ERR_ARG; }
+    if (create_flags & ~DYT_CREATE_WIDE_HEAD) { set_error("dyt_ctx_create_ex: unknown create_flags 0x%x (known: DYT_CREATE_WIDE_HEAD = 0x%x)", create_flags, DYT_CREATE_WIDE_HEAD); return DYT_ERR_ARG; }
+    const bool wide = (create_flags & DYT_CREATE_WIDE_HEAD) != 0;
+    if (wide && cfg->num_classes > 65536) {
+        set_error("unsupported config: num_classes=%d (1..65536 with DYT_CREATE_WIDE_HEAD; 1..1024 without)", cfg->num_classes);
+        return DYT_ERR_ARG;
+    }
+    if (wide && cfg->frames > 1) { set_error("wide head: image model only (DYT_CREATE_WIDE_HEAD with frames=%d)", cfg->frames); return DYT_ERR_ARG; }
     if (cfg->ffn_num < 1 || cfg->ffn_num > RP || cfg->depth < 1 || cfg->depth > 64 || cfg->max_batch < 1 ||
-        cfg->num_classes < 1 || cfg->num_classes > 1024 || cfg->slots < 1 || cfg->slots > 4 ||
+        cfg->num_classes < 1 || (!wide && cfg->num_classes > 1024) || cfg->slots < 1 || cfg->slots > 4 ||
         (cfg->precision != DYT_PREC_FP32 && cfg->precision != DYT_PREC_BF16)) {
-        set_error("unsupported config: ffn_num=%d (1..64) depth=%d max_batch=%d num_classes=%d (1..1024) slots=%d precision=%d",
-                  cfg->ffn_num, cfg->depth, cfg->max_batch, cfg->num_classes, cfg->slots, cfg->precision);
+        set_error("unsupported config: ffn_num=%d (1..64) depth=%d max_batch=%d num_classes=%d (%s) slots=%d precision=%d",
+                  cfg->ffn_num, cfg->depth, cfg->max_batch, cfg->num_classes, wide ? "1..65536" : "1..1024", cfg->slots, cfg->precision);
         return DYT_ERR_ARG;
     }
     int ndev = 0;
@@ -349,6 +359,7 @@ extern "C" int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out) {
     dyt_ctx* c = new dyt_ctx();
     c->cfg = *cfg;
     c->inf = cfg->inference_only != 0;
+    c->wide_head = wide;
     c->prec = cfg->precision;
     c->frames = cfg->frames > 1 ? cfg->frames : 1;
     c->ad_ln = cfg->adapter_ln;

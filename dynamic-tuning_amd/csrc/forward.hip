@@ -410,6 +410,9 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     } else if (c->frames > 1) {
         int rc = pool_forward(c, S, trainable, logits, B, s);
         if (rc) return rc;
+    } else if (c->wide_head) {
+        RUN(2, 0, launch_head_wide_fwd(S.xs[depth], (size_t)NT * D, c->norm_w, c->norm_b, trainable + c->off_hw, trainable + c->off_hb, S.cls_n,
+                                       S.head_stats, logits, B, c->cfg.num_classes, s));
     } else {
         RUN(2, 0, launch_head_fwd(S.xs[depth], c->norm_w, c->norm_b, trainable + c->off_hw, trainable + c->off_hb, S.cls_n,
                                   S.head_stats, logits, B, c->cfg.num_classes, s));

@@ -217,6 +217,15 @@ int launch_head_fwd(const float* x, const float* nw, const float* nb, const floa
 int launch_head_bwd(const float* dlogits, const float* x, const float* cls_n, const float2* stats,
                     const float* nw, const float* hw, float* g, float* dWh, float* dbh, int batch, int C,
                     int compact, hipStream_t s);  // compact: g is [B,768] (cls rows only), no zero fill
+// The same head for up to 65 536 classes on exact-fp32 MFMA kernels (head_wide.hip, DYT_CREATE_WIDE_HEAD): another summation order
+// than the row kernels above, so a separate form.  x row b at x + b * x_stride; part = head_wide_scratch_floats(batch, C) floats
+// ([ceil(C/1024) class slices][batch][768] partial sums of dx); g / dWh / dbh may each be null (not computed).
+size_t head_wide_scratch_floats(int batch, int C);
+int launch_head_wide_fwd(const float* x, size_t x_stride, const float* nw, const float* nb, const float* hw, const float* hb,
+                         float* cls_n, float2* stats, float* logits, int batch, int C, hipStream_t s);
+int launch_head_wide_bwd(const float* dlogits, const float* x, size_t x_stride, const float* cls_n, const float2* stats,
+                         const float* nw, const float* hw, float* g, float* dWh, float* dbh, int batch, int C, int compact,
+                         float* part, hipStream_t s);
 
 struct LossArgs {
     const float* logits_s; const float* logits_t; const int64_t* targets;

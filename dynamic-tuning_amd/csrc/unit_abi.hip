@@ -331,6 +331,26 @@ extern "C" int dyt_adapter_bwd(const float* x, const float* down_w, const float*
     return DYT_OK;
 }
 
+// The wide head alone (head_wide.hip): the launches of forward_impl / backward_impl under DYT_CREATE_WIDE_HEAD, on caller-supplied rows.
+extern "C" int dyt_head_wide(const float* cls_x, const float* norm_w, const float* norm_b, const float* head_w, const float* head_b,
+                             float* logits, const float* dlogits, float* dx, float* d_head_w, float* d_head_b, int batch, int C, void* stream) {
+    if (!cls_x || !norm_w || !norm_b || !head_w || !head_b || !logits || batch < 1 || C < 1 || C > 65536) { set_error("dyt_head_wide: bad argument (batch %d, C %d: 1..65536)", batch, C); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    float* cls_n = (float*)sc.get((size_t)batch * D * 4);
+    float2* stats = (float2*)sc.get((size_t)batch * sizeof(float2));
+    float* part = dlogits && dx ? (float*)sc.get(head_wide_scratch_floats(batch, C) * 4) : nullptr;
+    if (!cls_n || !stats || (dlogits && dx && !part)) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+    int rc = launch_head_wide_fwd(cls_x, (size_t)D, norm_w, norm_b, head_w, head_b, cls_n, stats, logits, batch, C, s);
+    if (rc) return rc;
+    if (dlogits) {
+        rc = launch_head_wide_bwd(dlogits, cls_x, (size_t)D, cls_n, stats, norm_w, head_w, dx, d_head_w, d_head_b, batch, C, 1, part, s);
+        if (rc) return rc;
+    }
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
 // The token-gathered MLP of block `layer` with the context's frozen weights (reference models/model_speed_test.py:297-305):
 // x [B*197,768] += scatter(fc2(gelu(fc1(LN2(gather(u, mask)))))) for the tokens whose mask is non-zero; u, x fp32, mask [B*197].
 extern "C" int dyt_mlp_gathered_fwd(dyt_ctx* c, int layer, const float* u, const float* mask, float* x, int batch, int32_t* total_out,

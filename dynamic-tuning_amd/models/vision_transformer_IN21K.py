@@ -13,7 +13,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from _lib import DyTError, OPT_COUNT_FLOPS_TOKENS, inference_only_default, key_to_param, is_trainable_param
+from _lib import DyTError, OPT_COUNT_FLOPS_TOKENS, inference_only_default, key_to_param, wide_head_default, is_trainable_param
 from runtime import DyTEngine, parse_precision
 from .dynamic_adapter import Adapter, TokenSelect, _LinearParams
 
@@ -189,7 +189,7 @@ class VisionTransformer(nn.Module):
                  no_embed_class=False, pre_norm=False, fc_norm=None, drop_rate=0., pos_drop_rate=0., patch_drop_rate=0.,
                  proj_drop_rate=0., attn_drop_rate=0., drop_path_rate=0., weight_init='', embed_layer=None,
                  norm_layer=None, act_layer=None, block_fn=Block, mlp_layer=None, tuning_config=None, select_config=None,
-                 precision=None, max_batch=None, train_mode=None, inference_only=None):
+                 precision=None, max_batch=None, train_mode=None, inference_only=None, wide_head=None):
         super().__init__()
         fixed = dict(img_size=(img_size, 224), patch_size=(patch_size, 16), in_chans=(in_chans, 3), embed_dim=(embed_dim, 768),
                      num_heads=(num_heads, 12), mlp_ratio=(mlp_ratio, 4.0), qkv_bias=(qkv_bias, True), global_pool=(global_pool, 'token'),
@@ -242,6 +242,9 @@ class VisionTransformer(nn.Module):
         # for eval forwards alone (dyt_config.inference_only: a fraction of the training arena, any batch size that fits); train() mode, a
         # forward that would record a graph, train_step and as_fused raise DyTError
         self.inference_only = inference_only_default(inference_only, tuning_config)
+        # wide_head (keyword, else tuning_config.dyt_wide_head, else env DYT_WIDE_HEAD, else num_classes > 1024): the head on the library's
+        # MFMA kernels (DYT_CREATE_WIDE_HEAD, up to 65 536 classes: --nb_classes 21843) instead of the row kernels (up to 1024)
+        self.wide_head = wide_head_default(wide_head, tuning_config, num_classes)
         self._engine = None
         self._sync_state = None
         self._seed_counter = 0
@@ -285,7 +288,8 @@ class VisionTransformer(nn.Module):
                             precision=self.precision, max_batch=mb, depth=self.depth,
                             adapter_dropout=self.blocks[0].adaptmlp.dropout, tau=self.blocks[0].mlp_token_select.tau,
                             threshold=self.blocks[0].mlp_token_select.threshold, frames=self._frames or 1,
-                            adapter_ln=self.blocks[0].adaptmlp.adapter_ln_code, inference=self.inference_only)
+                            adapter_ln=self.blocks[0].adaptmlp.adapter_ln_code, inference=self.inference_only,
+                            wide_head=self.wide_head)
             self._engine = eng
             self._sync_state = None
         if not self.inference_only and getattr(eng, "drop_path_rate", 0.0) != self.drop_path_rate:   # (stochastic depth: training passes only)

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from _lib import (Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
+from _lib import (CREATE_WIDE_HEAD, Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
                   F_TRAINING, OPT_F32_SPLIT16, OPT_LEARNABLE_SCALE, PREC_BF16, PREC_FP16, PREC_FP16X3, PREC_FP16F8, PREC_FP16X3F, PREC_FP16X3H, PREC_FP16X3Q, PREC_FP32,
                   check, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
 
@@ -41,7 +41,7 @@ def parse_precision(p):
 
 class DyTEngine:
     def __init__(self, num_classes, ffn_num, adapter_scale, device, precision=PREC_BF16, max_batch=128, depth=12,
-                 slots=2, adapter_dropout=0.1, tau=5.0, threshold=0.5, frames=1, adapter_ln=0, inference=False):
+                 slots=2, adapter_dropout=0.1, tau=5.0, threshold=0.5, frames=1, adapter_ln=0, inference=False, wide_head=False):
         if torch.device(device).type != "cuda":
             raise DyTError("the DyT path runs on a HIP device only (got %s); there is no CPU path" % (device,))
         self.device = torch.device(device)
@@ -66,9 +66,15 @@ class DyTEngine:
         self.adapter_ln = int(adapter_ln)
         self.frames = max(1, int(frames))   # > 1: video model, every batch is clips * frames images
         self.L = lib(fp16=self.precision == PREC_FP16 or split != 0)
+        # wide_head=True (DYT_CREATE_WIDE_HEAD): the head on the exact-fp32 MFMA kernels, num_classes up to 65 536; False: the row-kernel
+        # head (up to 1024 classes), bit for bit what every measured configuration runs
+        self.wide_head = bool(wide_head)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            self._ck(self.L.dyt_ctx_create(ctypes.byref(self.cfg), ctypes.byref(h)))
+            if self.wide_head:
+                self._ck(self.L.dyt_ctx_create_ex(ctypes.byref(self.cfg), CREATE_WIDE_HEAD, ctypes.byref(h)))
+            else:
+                self._ck(self.L.dyt_ctx_create(ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h
         if split:
             with torch.cuda.device(self.device):

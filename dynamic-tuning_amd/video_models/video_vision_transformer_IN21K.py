@@ -51,7 +51,9 @@ class VisionTransformer(_ImageViT):
     """Reference :282-483."""
 
     def __init__(self, *args, inference_only=None, **kwargs):
-        super().__init__(*args, inference_only=inference_only, **kwargs)
+        if "wide_head" in kwargs:
+            raise TypeError("the video model has no wide_head keyword: its pooling head is not part of the wide-head form")
+        super().__init__(*args, inference_only=inference_only, wide_head=False, **kwargs)   # (> 1024 classes: the library's refusal)
         self.query_token = nn.Parameter(torch.zeros(1, 1, self.embed_dim))          # :407
         self.attentive_blocks = AttentiveBlock(self.embed_dim, 12, qkv_bias=True)   # :408-410
         self.attentive_blocks.apply(self.init_weights)

@@ -146,6 +146,18 @@ int dyt_version(void);
 int dyt_operand_type(void);
 
 int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out);
+/* dyt_ctx_create with creation flags (ABI v4); dyt_ctx_create(cfg, out) is dyt_ctx_create_ex(cfg, 0, out).  Unknown bits: DYT_ERR_ARG.
+ *   DYT_CREATE_WIDE_HEAD  the classification head (final LayerNorm of the cls rows + Linear(768, num_classes), forward and backward)
+ *                         runs as exact-fp32 MFMA GEMMs (csrc/head_wide.hip) and num_classes may be 1 ... 65 536 -- the
+ *                         ImageNet-21K classifier has 21 843 rows -- instead of the row kernels' 1 ... 1024.  An explicit form, not a
+ *                         lifted limit: the wide kernels sum in another order (the head's dx over class slices of 1024 added in
+ *                         ascending order), so their results differ from the row kernels' in the last bits and the row-kernel head
+ *                         stays the bit-pinned default.  Below 1025 classes both forms run on the same weights.  fp32 arithmetic in
+ *                         every precision mode, no atomics: bit-reproducible run to run.  Image model only (frames > 1: DYT_ERR_ARG);
+ *                         valid together with dyt_config::inference_only.  Adds [ceil(C/1024)][max_batch][768] floats per slot to
+ *                         the training layout. */
+#define DYT_CREATE_WIDE_HEAD 1u
+int dyt_ctx_create_ex(const dyt_config* cfg, uint32_t create_flags, dyt_ctx** out);
 int dyt_ctx_destroy(dyt_ctx* ctx);
 /* bytes of device memory the context holds (weights + workspace) */
 int dyt_ctx_bytes(const dyt_ctx* ctx, int64_t* bytes);
@@ -395,6 +407,12 @@ int dyt_adapter_fwd(const float* x, const float* down_w, const float* down_b, co
 int dyt_adapter_bwd(const float* x, const float* down_w, const float* down_b, const float* up_w, const float* dout, float* dx,
                     float* d_down_w, float* d_down_b, float* d_up_w, float* d_up_b, int M, int r, float scale, float drop_p,
                     const uint8_t* keep_mask, uint64_t seed, int precision, void* stream);
+/* The wide head (DYT_CREATE_WIDE_HEAD) without a context, exactly the launches the context path runs: logits [B,C] = LN(cls_x) head_w^T
+ * + head_b (final LayerNorm norm_w / norm_b, eps 1e-6; cls_x [B,768] the un-normalised cls rows).  With dlogits [B,C] also its
+ * backward: dx [B,768] = the gradient w.r.t. cls_x (may be NULL), d_head_w [C,768] / d_head_b [C] ACCUMULATED (each may be NULL).
+ * dlogits NULL: forward only, no gradient is touched.  C = 1 ... 65 536. */
+int dyt_head_wide(const float* cls_x, const float* norm_w, const float* norm_b, const float* head_w, const float* head_b,
+                  float* logits, const float* dlogits, float* dx, float* d_head_w, float* d_head_b, int batch, int C, void* stream);
 /* the token-gathered MLP of block `layer` (frozen weights of the context; models/model_speed_test.py:297-305): for the tokens with a
  * non-zero mask, x[t] += fc2(gelu(fc1(LN2(u[t])))); u, x fp32 [batch*197,768] (x in place), mask [batch*197]; total_out[1] (device,
  * may be NULL) = number of gathered tokens */
