@@ -1489,7 +1489,7 @@ int launch_attn_bwd(int precision, const void* q, const void* k, const void* v, 
             if (set_lds((const void*)attn_bwd_dkv_split_kernel<3>, lds2) || set_lds((const void*)attn_bwd_dkv_split_kernel<1>, lds2)) return -2;
             done[dev & 63] = true;
         }
-        static const float gs_unit = getenv("DYT_SPLIT_ATTN_GS") ? (float)atof(getenv("DYT_SPLIT_ATTN_GS")) : 4096.0f;   // unit entries (no context)
+        constexpr float gs_unit = 4096.0f;   // unit entries (no context)
         auto* kq = grad_parts >= 3 ? attn_bwd_dq_split_kernel<3> : attn_bwd_dq_split_kernel<1>;
         auto* kkv = grad_parts >= 3 ? attn_bwd_dkv_split_kernel<3> : attn_bwd_dkv_split_kernel<1>;
         hipLaunchKernelGGL(kq, dim3(min(grid, 256)), dim3(448), lds1, s, (const float*)q, (const float*)k, (const float*)v,

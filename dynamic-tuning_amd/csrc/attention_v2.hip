@@ -668,13 +668,11 @@ int launch_attn_fwd_v2(const void* q, const void* k, const void* v, void* out, f
     const int grid = batch * NH;
     const size_t lds = 5 * av2::IMG;
     static bool done[64] = {};
-    static const int pipe = getenv("DYT_ATTN_V2_PIPE") ? atoi(getenv("DYT_ATTN_V2_PIPE")) : 1;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     if (!done[dev & 63]) {
-        if (set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true>, lds) || set_lds_v2((const void*)av2::attn_fwd_v2_kernel<false>, lds) ||
-            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true>, lds) ||
-            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, false, false>, lds) || set_lds_v2((const void*)av2::attn_fwd_v2_kernel<false, 0, false, false>, lds) ||
+        if (set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true>, lds) || set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true>, lds) ||
+            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, false, false>, lds) ||
             set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true, false>, lds)) return -2;
         done[dev & 63] = true;
     }
@@ -685,8 +683,7 @@ int launch_attn_fwd_v2(const void* q, const void* k, const void* v, void* out, f
         DYT_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    auto* kern = lse ? (pipe ? av2::attn_fwd_v2_kernel<true> : av2::attn_fwd_v2_kernel<false>)
-                     : (pipe ? av2::attn_fwd_v2_kernel<true, 0, false, false> : av2::attn_fwd_v2_kernel<false, 0, false, false>);
+    auto* kern = lse ? av2::attn_fwd_v2_kernel<true> : av2::attn_fwd_v2_kernel<true, 0, false, false>;   // (PIPE = false: tools/probes/r5/av2_test.hip only)
     hipLaunchKernelGGL(kern, dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, lse, grid);
     DYT_HIP_CHECK(hipGetLastError());
     return 0;

@@ -154,7 +154,7 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
     ReduceQueue rq;   // adapter weight-gradient / gate-gradient reductions: queued per block, flushed where the gradients must be final
     bool prepped = false;  // the previous iteration's ln_bwd already produced g_at / dmask for this block
     bool g3_ready = false; // ... and (fp32 split form) T.g3 = g as the 16-bit split operand of this block's GELU' dgrad
-    const bool split_prod = split16 && c->split_prod;
+    const bool split_prod = split16;   // ln_bwd / tok_bwd write the split operand of the GEMM that follows
     for (int l = depth - 1; l >= 0; --l) {
         const LayerW& W = c->W[l];
         LayerS& L = S.L[l];
@@ -222,7 +222,7 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
             b.out_xsum = nullptr; b.alpha_x = 0.f;
             b.out_ysum = gbase + c->off_db; b.alpha_y = inv_gs;                     // down_proj.bias
             b.alpha_dev = ddz_unlift;
-            if (split16 && c->split_bwd_parts == 1 && c->split_wgrad16) {   // "fp16x3f": gradient products one-part here too
+            if (split16 && c->split_bwd_parts == 1) {   // "fp16x3f": gradient products one-part here too
                 a.half_products = b.half_products = true;
                 a.x_scale = c->split_gs;   // X = g (gradient-sized), Y = d_act
                 b.y_scale = c->split_gs;   // X = u, Y = ddz (gradient-sized)

@@ -135,7 +135,7 @@ struct dyt_ctx {
     size_t aux_size = 0;
     bool aux_bwd16 = false;     // the aux arena holds the bwd16 buffers
     int f8_mask_complete = 0;   // ... of a complete_model (teacher) pass: no token-keep decision depends on it (its gate output is discarded), only its logits -- "fp16x3q": 15 + 32 (32 = its attention forward as the hi * hi product alone)
-    int f8_mask = 0;            // classes of forward GEMMs in that form: 1 qkv, 2 proj, 4 fc1, 8 fc2, 16 patch embedding (DYT_F8_CLASSES; "fp16f8" = 31, "fp16x3q" = 3)
+    int f8_mask = 0;            // classes of forward GEMMs in that form: 1 qkv, 2 proj, 4 fc1, 8 fc2, 16 patch embedding ("fp16f8" = 31, "fp16x3q" = 3)
     bool f8 = false;            // "fp16f8": forward GEMMs as hi * hi on the f16 matrix cores + the two correction products on the fp8 ones (DYT_OPT_F32_SPLIT16 = 4; implies bwd16)
     int* pe_w_exp = nullptr; unsigned* f8_scratch = nullptr;
     bool bwd16 = false;         // "fp16x3h": the fp16x3 forward, the backward on the 16-bit mode's operands and kernels (DYT_OPT_F32_SPLIT16 = 3)
@@ -149,14 +149,10 @@ struct dyt_ctx {
     void *ad_down_w, *ad_down_wT, *ad_up_w, *ad_up_wT;
     float* ad_down_b;
     bool split_attn = true;     // ... and the attention forward too (attn_fwd_split_kernel; DYT_SPLIT_ATTN=0: exact fp32 MFMA kernel)
-    bool split_prod = true;     // ... attention forward / ln_bwd / tok_bwd write the split operand of the GEMM that follows (DYT_SPLIT_PROD=0: pre-passes)
-    float split_gs = 4096.0f;   // ... their gradient operands are multiplied by this power of two before the split (DYT_SPLIT_GS_LOG2)
-    int split_bwd_parts = 3;    // ... products of the GRADIENT GEMMs' contraction (DYT_SPLIT_BWD_PARTS: 3 full, 2 = dY_hi * (W_hi + W_lo), 1 = dY_hi * W_hi)
+    float split_gs = 4096.0f;   // ... their gradient operands are multiplied by this power of two before the split
+    int split_bwd_parts = 3;    // ... products of the GRADIENT GEMMs' contraction (3 full, 1 = dY_hi * W_hi: "fp16x3f")
     int split_bwd_attn_parts = 3;   // ... and of the split attention backward's dP / dQ / dK / dV products (3 or 1; the score recomputation keeps three)
     const float* soft_targets = nullptr; int soft_batch = 0;   // dyt_set_soft_targets: class-probability targets of the next loss evaluations
-    int one_part_complete = 0;  // ... classes of a complete_model (teacher) pass contracted as hi * hi alone (SPLIT_F)
-    int split_fwd_parts[4] = {3, 3, 3, 3};   // ... products of the FORWARD GEMMs per class (qkv, proj, fc1, fc2): measurement knob
-    bool split_wgrad16 = true;  // ... adapter weight gradients as one-part products too (DYT_SPLIT_WGRAD16=0: the exact-fp32 kernel)
     bool split16 = false;       // fp32 mode: frozen-weight GEMMs as three 16-bit MFMA products (DYT_OPT_F32_SPLIT16)
     void* pe_w3 = nullptr;
     // 16-bit modes: LayerNorm-2 is not a kernel -- the proj epilogue emits per-row partial statistics of u, fc1 contracts the 16-bit copy
@@ -284,13 +280,10 @@ struct ProfScope {
         if (_rc) return _rc;                   \
     } while (0)
 #define SPLIT(a, w3) do { if (c->split16) { (a).W3 = (w3); (a).a3 = T.a3; } } while (0)
-// forward GEMM class g (0 qkv, 1 proj, 2 fc1, 3 fc2): products of its contraction (measurement knob DYT_SPLIT_FWD_PARTS="qkv,proj,fc1,fc2")
+// forward GEMM class g (0 qkv, 1 proj, 2 fc1, 3 fc2) in the three-part or, where the pass's class mask fm says so, the fp8-correction form
 // (w3b: the class's second image, used by the pass whose form differs from the student's)
-// one_part (bit g; complete_model passes only): the class's GEMM as the hi * hi product alone -- both operand images carry the IEEE-half hi part in
-// front of either form's second part (same row stride), so the image the pass would read anyway serves
-#define SPLIT_F(a, w3, w3b, g) do { SPLIT(a, (((fm ^ c->f8_mask) >> (g)) & 1) ? (w3b) : (w3)); if (c->split16) (a).a3_parts = c->split_fwd_parts[g]; \
-        if (c->split16 && ((one_part >> (g)) & 1)) (a).a3_parts = 1; \
-        else if ((fm >> (g)) & 1) { (a).f8 = true; (a).w_exp = W.w_exp + (g); } } while (0)
+#define SPLIT_F(a, w3, w3b, g) do { SPLIT(a, (((fm ^ c->f8_mask) >> (g)) & 1) ? (w3b) : (w3)); \
+        if ((fm >> (g)) & 1) { (a).f8 = true; (a).w_exp = W.w_exp + (g); } } while (0)
 // gradient operands: scaled by 2^12 before the split so that the lo parts stay fp16 normals (the loss scale of the fp16 mode)
 // the producing kernel already wrote the split operand into `buf`
 #define SPLIT_READY(a, buf) do { if (c->split16) { (a).a3 = (buf); (a).a3_ready = true; } } while (0)

@@ -608,6 +608,9 @@ hipEvent_t dyt::get_event(dyt_ctx* c) {
     return e;
 }
 
+// environment DYT_SPLIT_ATTN=0: the split modes keep the exact-fp32 attention kernels (include/dyt_hip.h)
+static bool split_attn_env() { const char* e = getenv("DYT_SPLIT_ATTN"); return !e || atoi(e) != 0; }
+
 extern "C" int dyt_ctx_set_option(dyt_ctx* c, int option, int value) {
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
     switch (option) {
@@ -640,8 +643,6 @@ extern "C" int dyt_ctx_set_option(dyt_ctx* c, int option, int value) {
             // ... and the complete_model (teacher) pass of 5 takes the fp8-correction form for the MLP as well: its gate output is discarded, no
             // token-keep decision depends on it, only its logits (5e-5 from the reference instead of 7e-6) -- the dense pass is the heavier one
             c->f8_mask_complete = value == 4 ? 31 : (value == 5 ? 15 + 32 : 0);   // (32: that pass's attention forward as the hi * hi product alone)
-            if (const char* e = getenv("DYT_F8_CLASSES")) { if (c->f8) c->f8_mask = c->f8_mask_complete = atoi(e) & 31; }   // measurement knobs
-            if (const char* e = getenv("DYT_F8_CLASSES_COMPLETE")) { if (c->f8) c->f8_mask_complete = atoi(e) & 63; }   // (32: that pass's attention forward as the hi * hi product alone)
             c->f8_mask_complete = (c->f8_mask_complete & ~16) | (c->f8_mask & 16);   // the patch embedding is shared between the passes
             c->gs = 1.0f;
 #ifdef DYT_FP16
@@ -650,14 +651,7 @@ extern "C" int dyt_ctx_set_option(dyt_ctx* c, int option, int value) {
             // 2 ("fp16x3f"): the forward (logits, gate decisions, losses, saved activations) as in 1; the gradient GEMMs contract
             // dY_hi * W_hi alone and the attention backward's dP / dQ / dK / dV take the hi * hi product (its score recomputation keeps three)
             c->split_bwd_parts = c->split_bwd_attn_parts = value == 2 ? 1 : 3;
-            if (const char* e = getenv("DYT_SPLIT_GS_LOG2")) c->split_gs = (float)(1u << atoi(e));   // measurement knob
-            if (const char* e = getenv("DYT_SPLIT_BWD_PARTS")) c->split_bwd_parts = std::min(3, std::max(1, atoi(e)));
-            if (const char* e = getenv("DYT_SPLIT_BWD_ATTN_PARTS")) c->split_bwd_attn_parts = atoi(e) >= 3 ? 3 : 1;
-            if (const char* e = getenv("DYT_SPLIT_FWD_PARTS")) sscanf(e, "%d,%d,%d,%d", &c->split_fwd_parts[0], &c->split_fwd_parts[1], &c->split_fwd_parts[2], &c->split_fwd_parts[3]);
-            if (const char* e = getenv("DYT_SPLIT_WGRAD16")) c->split_wgrad16 = atoi(e) != 0;
-            if (const char* e = getenv("DYT_SPLIT_ATTN")) c->split_attn = atoi(e) != 0;
-            if (const char* e = getenv("DYT_SPLIT_PROD")) c->split_prod = atoi(e) != 0;
-            if (c->bwd16) c->split_attn = c->split_prod = true;   // the 16-bit backward reads what the split attention kernel / producers write (planes, the per-layer proj operand image)
+            c->split_attn = c->bwd16 || split_attn_env();   // the 16-bit backward reads what the split attention kernel writes (planes, the per-layer proj operand image)
             for (auto& S : c->slots) S.valid = false;
             if (c->split16) {   // parts of the weights uploaded so far (later dyt_set_frozen calls refresh theirs)
                 DYT_HIP_CHECK(hipDeviceSynchronize());   // uploads may be in flight on the caller's streams

@@ -176,8 +176,6 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     const bool use_gate = !complete || (flags & DYT_F_GATE_ALWAYS);
     const float drop_p = training ? c->cfg.adapter_dropout : 0.f;
     const uint64_t* seed_dev = (flags & DYT_F_DEVICE_SEED) ? c->seed_dev : nullptr;
-    static const int one_part_env = getenv("DYT_ONE_PART_COMPLETE") ? atoi(getenv("DYT_ONE_PART_COMPLETE")) : -1;   // measurement knob (bit per class: qkv 1, proj 2, fc1 4, fc2 8)
-    const int one_part = (c->split16 && complete) ? (one_part_env >= 0 ? one_part_env : c->one_part_complete) : 0;
     const int fm = c->split16 ? (complete ? c->f8_mask_complete : c->f8_mask) : 0;   // classes (qkv 1, proj 2, fc1 4, fc2 8, embed 16) whose split operands are in the hi16 / fp8 form
     const bool planes = c->bwd16 && c->split16 && c->split_attn;   // q / k / v as 16-bit hi + lo planes (QKV epilogue -> split attention kernel; hi = what a 16-bit backward reads)
     const bool save16 = save && planes;   // "fp16x3h": what the backward reads is saved in the 16-bit operand type
@@ -245,7 +243,7 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
                 if (planes) { a.out_at = L.q16; a.out_at2 = L.k16; a.out_at3 = L.v16; a.qkv_lo[0] = T.qlo; a.qkv_lo[1] = T.klo; a.qkv_lo[2] = T.vlo; }
                 RUN_GEMM(EPI_QKV, a);
             }
-            void* ao3 = (c->split16 && c->split_attn && c->split_prod) ? ((save16 && L.ao3) ? L.ao3 : T.g3) : nullptr;   // the split attention kernel also writes the proj GEMM's operand
+            void* ao3 = (c->split16 && c->split_attn) ? ((save16 && L.ao3) ? L.ao3 : T.g3) : nullptr;   // the split attention kernel also writes the proj GEMM's operand
             // last block of a pass without a gate (teacher / complete model): the proj GEMM runs on the gathered cls rows of the fp32 output
             const bool tail_proj = c->cls_tail && l == depth - 1 && l > 0 && !tokens_out && !use_gate;
             AttnSave16 sv16{L.q16, L.k16, L.v16, nullptr};   // (the output's 16-bit copy is the hi plane of ao3)
@@ -295,8 +293,7 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
         // contracted by the fc2 kernel as three leading tiles in front of its main loop (gemm.hip: LEAD); the dropped tokens' up-projection launch
         // runs on the same two images.  Until round 5 these modes ran the up-projection on the exact-fp32 MFMA kernel: an fp32
         // read-modify-write of [M,768] per block and pass (47 us) in front of the fc2 epilogue's own.
-        static const bool cat3_env = !(getenv("DYT_FC2_CAT3") && atoi(getenv("DYT_FC2_CAT3")) == 0);   // measurement switch: 0 = the round-5 two-launch form in the split modes only
-        const bool cat3 = cat3_env && !ad_out && c->fc2_cat && P == 0 && c->split16 && c->bwd16 && T.dact3 && c->ad_up_w3 && !masked_dense && !dp2;
+        const bool cat3 = !ad_out && c->fc2_cat && P == 0 && c->split16 && c->bwd16 && T.dact3 && c->ad_up_w3 && !masked_dense && !dp2;
         L.h_has_adapter = (cat || cat3) && need_h;   // the saved "MLP output" of this block then includes the adapter: tok_bwd corrects <g, h>
         FORK(sb);
         if (ad_in) RUN_ON(sb, 2, 0, launch_adapter_ln_fwd(P, L.u, aln_w, aln_b, T.xa, L.st_a, nullptr, Mr, s));
@@ -371,8 +368,7 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
                 // (round 6b: over the list of dropped rows like the 16-bit modes' launch -- gathered operand rows, scattered output rows -- instead of
                 // every row tile with the kept rows masked: 54 -> ~18 us)
                 up.W3 = up_w3; up.a3 = T.dact3; up.a3_ready = true; up.scale = 1.0f; up.bias_scale = ad_scale;
-                static const bool drop_list = !(getenv("DYT_CAT3_DROP_LIST") && atoi(getenv("DYT_CAT3_DROP_LIST")) == 0);
-                if (drop_list && T.drop_src) { up.a3_mapped = true; up.a_map = T.drop_src; up.row_map = T.drop_src; up.m_dev = L.total + 1; }
+                if (T.drop_src) { up.a3_mapped = true; up.a_map = T.drop_src; up.row_map = T.drop_src; up.m_dev = L.total + 1; }
                 else up.row_mask = L.maskf;
             } else if (fold2) {   // over the dispatcher's list of dropped rows (gather + scatter) instead of every row with the kept ones skipped
                 up.a_map = T.drop_src; up.row_map = T.drop_src; up.m_dev = L.total + 1;

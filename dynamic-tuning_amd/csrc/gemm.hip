@@ -511,8 +511,7 @@ struct CatArgs { const bf16* A2; const bf16* W2; const int* a2_map; float out_sc
 // main loop -- three-part fold form or fp8-correction form -- its registers and its schedule stay exactly the plain kernel's.  Three exposed
 // tile latencies per workgroup against the fp32 read-modify-write launch of [M,768] this replaces (adapter up-projection riding on fc2).   // f8_begin / w_exp: F8 kernels -- first fp8 k-tile, device word with the weight image's exponent   // a_ld: row stride of split operands when the contraction runs over fewer than three parts (0: K - a_fold * 64)
 // a_fold: k-tiles of ONE part of split operands stored [hi | lo] (row stride K - a_fold * 64): k-tile kt reads A column tile kt - (kt >= a_fold ? a_fold : 0) and W column tile kt - (kt >= 2 a_fold ? 2 a_fold : 0), i.e. [A_hi | A_hi | A_lo] x [W_hi | W_lo | W_hi]; 0 = plain   // out_scale: accumulators x this before the epilogue functor (split fp32 form; 1 elsewhere)
-// One workgroup = one tile: `bid` of `nwg` logical workgroups that tile rows [m_begin, M).  A device function so that one launch
-// can hold workgroups of two tile shapes (gemm_bf16_rows_kernel below).
+// One workgroup = one tile: `bid` of `nwg` logical workgroups that tile rows [m_begin, M) (gemm_bf16_nt_kernel below passes its block index).
 // F8 ("fp16f8" form of the split contraction, dyt_common.h: store4_split_f8): both operand images are [hi16 | 2K bytes of fp8]; k-tiles
 // [0, f8_begin) are f16 tiles of 64, the tiles after them fp8 tiles of 128 (the same 128 B per row and stage, the same fragment reads),
 // multiplied by v_mfma_scale_f32_16x16x128_f8f6f4 -- ONE instruction per fragment pair and k-tile instead of two, at the time of one
@@ -588,7 +587,7 @@ __device__ __forceinline__ void gemm_bf16_nt_tile(
                 // in scalar registers -- ONE vector register of addressing next to 128 accumulators and two fragment generations
                 // (per-lane row pointers spilled, and a spill reload inside the loop waits for vmcnt(0), i.e. for the DMA in flight).
                 // Hence no row gather and no clamp to the valid row count here: rows past it are read and never stored (the split
-                // operand images are padded to whole 256-row tiles; run_f8 sends gathered launches to the 128x128 kernel).
+                // operand images are padded to whole 256-row tiles; gemm_route sends gathered launches to the 128x128 kernel).
                 const bool isA = idx < A_INSTR;
                 const int piece = isA ? idx : idx - A_INSTR;
                 const size_t row0 = (size_t)((isA ? m0 : n0) + (piece * NW + wave_s) * 8);
@@ -1085,22 +1084,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void gemm_bf16_nt_kernel
     gemm_bf16_nt_tile<BM, BN, WAVES_M, WAVES_N, Epi, ABL, CAT, F8, LEAD>(A, W, M, N, K, m_dev, a_map, m_begin, epi, cat, blockIdx.x, gridDim.x);
 }
 
-// Narrow-N GEMM (N = 768) in ONE launch: the first n_big workgroups take 256x256 tiles of rows [0, body) -- whole rounds of the
-// 256 CUs --, the others 128x128 tiles (eight waves as 2x4) of rows [body, M).  Both shapes accumulate every dot product in the
-// same k order, so results do not depend on where the split falls; a compacted launch (device-side row count) leaves the
-// workgroups beyond the count with nothing to do instead of a second, empty launch.
-template <class Epi, bool CAT>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_rows_kernel(
-    const bf16* __restrict__ A, const bf16* __restrict__ W, int M, int N, int K, const int* __restrict__ m_dev,
-    const int* __restrict__ a_map, int body, int n_big, Epi epi, CatArgs cat) {
-    const int b = blockIdx.x;
-    if (b < n_big) gemm_bf16_nt_tile<256, 256, 2, 4, Epi, 0, CAT>(A, W, body, N, K, m_dev, a_map, 0, epi, cat, b, n_big);
-    else gemm_bf16_nt_tile<128, 128, 2, 4, Epi, 0, CAT>(A, W, M, N, K, m_dev, a_map, body, epi, cat, b - n_big, (int)gridDim.x - n_big);
-}
-
 }  // namespace dyt
 #include "gemm_bpre.h"
 #include "gemm_f32_mfma.h"
+#include "gemm_route.h"
 #include "gemm_skinny.h"
 namespace dyt {
 
@@ -1121,7 +1108,7 @@ static int launch_bf16_cfg(const GemmArgs& a, const Epi& epi, hipStream_t s, int
     constexpr int NTHR = 64 * WAVES_M * WAVES_N;
     if (m_end < 0) m_end = a.M;
     if (m_end <= m_begin) return 0;
-    const int grid = ((m_end - m_begin + BM - 1) / BM) * (a.N / BN);
+    const int grid = tile_grid(m_begin, m_end, a.N, BM, BN);
     const size_t lds = 2 * (BM + BN) * 64 * 2;
     auto kern = gemm_bf16_nt_kernel<BM, BN, WAVES_M, WAVES_N, Epi, ABL, CAT, F8, LEAD>;
     static bool attr_set[64] = {};   // per device: the attribute belongs to the (kernel, device) pair
@@ -1140,32 +1127,12 @@ static int launch_bf16_cfg(const GemmArgs& a, const Epi& epi, hipStream_t s, int
     return 0;
 }
 
-template <class Epi, bool CAT>
-static int launch_bf16_rows(const GemmArgs& a, const Epi& epi, hipStream_t s, int body) {
-    const int n_big = (body / 256) * (a.N / 256), n_small = ((a.M - body + 127) / 128) * (a.N / 128);
-    const size_t lds = 2 * (256 + 256) * 64 * 2;
-    auto kern = gemm_bf16_rows_kernel<Epi, CAT>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    DYT_HIP_CHECK(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        DYT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev & 63] = true;
-    }
-    const CatArgs cat{static_cast<const bf16*>(a.A2), static_cast<const bf16*>(a.W2), a.a2_map, a.out_scale, a.a_fold, a.a_ld, 0, nullptr};
-    hipLaunchKernelGGL(kern, dim3(n_big + n_small), dim3(512), lds, s, static_cast<const bf16*>(a.A), static_cast<const bf16*>(a.W), a.M, a.N,
-                       a.K, a.m_dev, a.a_map, body, n_big, epi, cat);
-    ++g_bf16_kernel_launches;
-    DYT_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 template <int ABL, class Epi>
 static int launch_bf16_bpre(const GemmArgs& a, const Epi& epi, hipStream_t s, int m_begin = 0, int m_end = -1) {
     if (m_end < 0) m_end = a.M;
     if (m_end <= m_begin) return 0;
     if (a.K % 256 != 0 || a.N % 256 != 0) { set_error("gemm_bpre: K=%d and N=%d must be multiples of 256", a.K, a.N); return -1; }
-    const int grid = ((m_end - m_begin + 127) / 128) * (a.N / 256);
+    const int grid = tile_grid(m_begin, m_end, a.N, 128, 256);
     hipLaunchKernelGGL((gemm_bf16_bpre_kernel<Epi, ABL>), dim3(grid), dim3(256), 0, s, static_cast<const bf16*>(a.A),
                        static_cast<const bf16*>(a.W), m_end, a.N, a.K, a.m_dev, a.a_map, m_begin, epi, a.out_scale);
     ++g_bf16_kernel_launches;
@@ -1188,133 +1155,63 @@ int get_gemm_splitk() {
     if (g_splitk < 0) { const char* e = getenv("DYT_SPLITK"); g_splitk = e ? (atoi(e) != 0) : 1; }
     return g_splitk;
 }
-static int g_big_tile_min_n = 2304;
-static int g_use_bpre = 1;        // wide-N GEMMs with a pre-shuffled frozen weight: 128x256 tiles, 2 workgroups / CU (gemm_bpre.h)
-static int g_split_rows = getenv("DYT_SPLIT_ROWS") ? atoi(getenv("DYT_SPLIT_ROWS")) : 1;   // (0: 128x128 tiles for every row -- measurement knob)
-//      // narrow-N GEMMs: 256x256 tiles for whole rounds of rows + 128x128 tiles for the rest  // N >= this (and % 256 == 0): 256x256 tiles with the half-stage pipeline
-
-// the "fp16f8" split contraction (a.K = 2 x the logical K: K / 64 f16 tiles + K / 64 fp8 tiles): tile shapes as for the three-part form
-template <class Epi, int LEAD = 0>
-static int run_f8(const GemmArgs& a, const Epi& epi, hipStream_t s) {
-    if (a.K % 256 != 0 || a.M <= 0 || a.N % 128 != 0 || a.f8_begin * 128 != a.K) { set_error("gemm f8 form: K=%d N=%d M=%d", a.K, a.N, a.M); return -1; }
-    if (LEAD && (!a.A2 || !a.W2)) { set_error("gemm f8 form: leading tiles need A2 and W2"); return -1; }
-    if (a.N % 256 == 0 && a.N >= 2304 && a.M >= 2048 && !a.a_map) return launch_bf16_cfg<256, 256, 2, 4, 0, Epi, false, true, LEAD>(a, epi, s);
-    // logical K <= 768, N = 768 (proj forward of the split modes): like the 16-bit modes' proj (run_bf16: shortk_n768) -- one launch of 128x128 tiles,
-    // two workgroups per CU, instead of a 256x256 body + a 128x128 row tail.  DYT_F8_SHORTK_SMALL=0: the body + tail scheme
-    static const int f8_shortk_small = getenv("DYT_F8_SHORTK_SMALL") ? atoi(getenv("DYT_F8_SHORTK_SMALL")) : 1;
-    if (f8_shortk_small && (a.K <= 2 * D || f8_shortk_small == 2) && a.N % 128 == 0 && a.N < 2304) return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, false, true, LEAD>(a, epi, s);
-    if (a.N % 256 == 0 && !a.a_map) {   // (the 256x256 fp8 kernel takes no row gather)
-        constexpr int NCU = 256;
-        const int tn = a.N / 256, t256 = ((a.M + 255) / 256) * tn, rounds = t256 / NCU, rem = t256 - rounds * NCU;
-        if (rounds >= 1 || rem >= 3 * NCU / 4) {
-            if (rem == 0 || rem >= 3 * NCU / 4) return launch_bf16_cfg<256, 256, 2, 4, 0, Epi, false, true, LEAD>(a, epi, s);
-            const int body = (rounds * NCU / tn) * 256;
-            int rc = launch_bf16_cfg<256, 256, 2, 4, 0, Epi, false, true, LEAD>(a, epi, s, 0, body);
-            if (rc) return rc;
-            return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, false, true, LEAD>(a, epi, s, body, a.M);
-        }
-    }
-    return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, false, true, LEAD>(a, epi, s);
+// what gemm_route() (gemm_route.h) reads of a GEMM
+static GemmShape route_shape(const GemmArgs& a, GemmFamily family, bool cat = false, bool lead = false, bool store_epi = false, bool splitk_epi = false) {
+    GemmShape g;
+    g.M = a.M; g.N = a.N; g.K = a.K; g.family = family; g.cat = cat; g.lead = lead; g.store_epi = store_epi;
+    g.wp = a.Wp != nullptr; g.a_map = a.a_map != nullptr; g.a_ld = a.a_ld != 0; g.a_fold = a.a_fold != 0; g.m_dev = a.m_dev != nullptr;
+    g.a2 = a.A2 != nullptr; g.w2 = a.W2 != nullptr; g.f8_begin = a.f8_begin;
+    g.splitk_fits = splitk_epi && family == GF_16 && get_gemm_splitk() && a.splitk_ws && !a.f8 &&
+                    (size_t)splitk_slices(a.K, cat) * a.M * a.N * sizeof(float) <= a.splitk_ws_bytes;
+    return g;
 }
-
-// wide-N GEMM against a pre-shuffled frozen weight -> gemm_bf16_bpre_kernel (see run_bf16)
-static bool takes_bpre(const GemmArgs& a, bool k768 = false) {
-    return a.Wp && g_use_bpre && a.N % 256 == 0 && a.K % 256 == 0 && (a.N >= g_big_tile_min_n || k768) && a.M >= 2048;
-}
-template <class Epi, bool CAT = false, int LEAD = 0>
-static int run_bf16(const GemmArgs& a, const Epi& epi, hipStream_t s) {
-    if (a.K % 64 != 0 || a.M <= 0) { set_error("gemm_bf16: K=%d must be a multiple of 64, M=%d", a.K, a.M); return -1; }
-    if constexpr (SplitKEpi<Epi>::value) {
-        // the K = 3072 GEMMs of the cls-only last block: split-K over 256-wide slices + a reduce launch that runs the functor (gemm_skinny.h).
-        // B = 128, serial: fc2 forward 56 -> see DESIGN.md 7d; DYT_OPT_GEMM_SPLITK 0 keeps the 6-tile launches
-        const int splitk = get_gemm_splitk();
-        const int slices = a.K / SK_SLICE + (CAT ? 1 : 0);
-        if (splitk && a.splitk_ws && a.M <= SK_MAX_M && a.K >= 1024 && a.K % SK_SLICE == 0 && a.N % 64 == 0 && !a.m_dev && !a.a_fold && !a.a_ld && !a.f8 &&
-            (size_t)slices * a.M * a.N * sizeof(float) <= a.splitk_ws_bytes && (!CAT || (a.A2 && a.W2))) {
-            hipLaunchKernelGGL((gemm_splitk_kernel<CAT>), dim3(a.N / 32, (a.M + 127) / 128, slices), dim3(256), 0, s, static_cast<const bf16*>(a.A),
-                               static_cast<const bf16*>(a.W), a.M, a.N, a.K, a.a_map, static_cast<const bf16*>(a.A2), static_cast<const bf16*>(a.W2),
-                               a.a2_map, a.splitk_ws);   // (not counted in g_bf16_kernel_launches: tools/pmc_traffic.py selects the gemm_bf16_* kernels)
-            hipLaunchKernelGGL((splitk_reduce_kernel<Epi>), dim3((unsigned)(((size_t)a.M * (a.N / 4) + 255) / 256)), dim3(256), 0, s, a.splitk_ws, slices, a.M,
-                               a.N, a.out_scale, epi);
-            DYT_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-    }
-    if constexpr (CAT) {
-        if (!a.A2 || !a.W2 || a.N % 128 != 0) { set_error("gemm_bf16: K-concatenated form needs A2, W2 and N %% 128 == 0 (N=%d)", a.N); return -1; }
-        // (Round 6: this form through the pre-shuffled-weight kernel -- the leading tile in its prologue's DMA round, bit-identical results -- measured
-        // 175 us serial against 123 + 28 us here and 23.4 vs 23.2 ms in the step: the fp32 read-modify-write epilogue of a 128x256 tile does not fit
-        // beside 128 accumulators -- 20-37 spilled registers.  Not kept; profiles/round6/r6_fc2_bpre_ab.txt.)
-    } else if constexpr (LEAD > 0) {
-        if (!a.A2 || !a.W2 || a.N % 128 != 0 || !a.a_fold) { set_error("gemm_bf16: leading three-part tiles need A2, W2, the split form and N %% 128 == 0 (N=%d)", a.N); return -1; }
-    } else {
-        if (a.A2) { set_error("gemm_bf16: this epilogue has no K-concatenated form"); return -1; }
-    // Wide-N GEMMs against a frozen weight: the pre-shuffled-weight kernel (128x256 tiles, two workgroups per CU, the
-    // weight never touches LDS).  In the step: 28.10 vs 28.40 ms with the 256x256 kernel; routing the N = 768 GEMMs
-    // through it as well gains another 0.5 % wall time but costs 8 % serial GEMM time, so they keep the split-row scheme.
-    // K = 768, N = 768 plain-store GEMMs (proj dgrad) take this kernel as well: with only 12 k-steps the 256x256 kernel's exposed
-    // prologue / epilogue (one workgroup per CU) weighs most: 45 vs 53.5 us serial.  (DYT_BPRE_K768: 0 off, 1 = every K = 768 GEMM
-    // with a pre-shuffled weight, i.e. the proj forward too -- measured 81.7 vs 73.3 us for that one, and the row kernels that read
-    // its fp32 output right after it got slower; 2 = default: those without a residual epilogue)
-    static const int bpre_k768 = getenv("DYT_BPRE_K768") ? atoi(getenv("DYT_BPRE_K768")) : 2;
-    // DYT_BPRE_STORE_MAXK: plain-store N = 768 GEMMs up to this K take the kernel as well.  Round 5: 3072 = the qkv dgrad (K = 2304) and the fc1 dgrad
-    // (K = 3072, compacted in the student pass) too.  In the serial profile they are slower there (GEMM family 20.2 -> 20.7 ms per step: the
-    // 256x256 kernel has the better main loop on warm operands), but the step -- what `value` measures -- is 23.85 vs 24.3 ms same-box, four
-    // alternations: 64 KB workgroups share CUs with the other pass's kernels, and the four-slot ring loses less on operands that come from
-    // HBM (tools/gemm_bench.py COLD=1: +22 % vs +42 %).  768 restores the round-4 routing (proj dgrad only).
-    static const int bpre_maxk = getenv("DYT_BPRE_STORE_MAXK") ? atoi(getenv("DYT_BPRE_STORE_MAXK")) : 3072;
-    const bool k768 = (a.K == D && bpre_k768 == 1) || (bpre_k768 == 2 && std::is_same<Epi, EpiStoreAT<bf16>>::value && a.K <= bpre_maxk);
-    if (takes_bpre(a, k768)) {
-        GemmArgs b = a; b.W = a.Wp;
-        return launch_bf16_bpre<0>(b, epi, s);
-    }
-    }
-    if constexpr (!CAT) {
-        // one-part split GEMMs with a wide N (GELU' dgrad of "fp16x3f": 12 k-tiles against an epilogue that reads gelu' and writes dZ):
-        // the 256x256 kernel's exposed epilogue outweighs its main loop -> 128x128 tiles, two workgroups per CU (DYT_SPLIT_SHORTK_SMALL=0: off)
-        static const int shortk_small = getenv("DYT_SPLIT_SHORTK_SMALL") ? atoi(getenv("DYT_SPLIT_SHORTK_SMALL")) : 1;   // 2: the N = 768 ones (proj dgrad) too
-        if (LEAD == 0 && shortk_small && a.a_ld && a.K <= D && (a.N >= g_big_tile_min_n || shortk_small == 2) && a.N % 128 == 0) return launch_bf16_cfg<128, 128, 2, 2, 0>(a, epi, s);
-    }
-    if (a.N % 256 == 0 && a.N >= g_big_tile_min_n && a.M >= 2048) return launch_bf16_cfg<256, 256, 2, 4, 0, Epi, CAT, false, LEAD>(a, epi, s);
-    if constexpr (!CAT) {
-        // K <= 768, N = 768 with a residual epilogue (proj forward, patch embedding): 12 k-steps against an epilogue that moves 194 MB -- the
-        // launch is bound by its epilogue traffic, and 1182 tiles of 128x128 on 512 slots interleave main loops and epilogues where 255 big
-        // tiles run them as two chip-wide phases: 74.6 vs 59 + 20.5 us (256x256 body + 128x128 row tail), step 24.98 vs 25.03 ms same-box,
-        // one launch instead of two; same k order, same bits.  DYT_SHORTK_N768_SMALL=0: the split-row scheme for these too
-        static const int shortk_n768 = getenv("DYT_SHORTK_N768_SMALL") ? atoi(getenv("DYT_SHORTK_N768_SMALL")) : 1;
-        if (LEAD == 0 && shortk_n768 && a.K <= D && a.N % 128 == 0 && a.M >= 2048 && !a.a_ld) return launch_bf16_cfg<128, 128, 2, 2, 0>(a, epi, s);
-    }
-    if (a.N % 256 == 0 && a.K >= 256 && g_split_rows) {
-        // Narrow-N GEMMs (N = 768): per row, 256x256 tiles are ~1.6x cheaper than 128x128 tiles (half the L2->LDS bytes
-        // per FLOP), but 99 x 3 = 297 tiles leave 41 for a second round.  The rows that fill whole rounds of 256
-        // CUs get 256x256 tiles, the remaining rows 128x128 tiles, as two launches on the same stream.  Both kernels
-        // accumulate every dot product in the same k order, so results do not depend on where the split falls.
-        // Compacted launches (device-side row count) leave the tail launch empty.  Measured in the step: 28.5 vs
-        // 29.1 ms (all-128x128) vs 28.8 ms (all-256x256, two rounds).
-        constexpr int NCU = 256;
-        const int tn = a.N / 256, t256 = ((a.M + 255) / 256) * tn, rounds = t256 / NCU, rem = t256 - rounds * NCU;
-        if (rounds >= 1 || rem >= 3 * NCU / 4) {
-            if (rem == 0 || rem >= 3 * NCU / 4) return launch_bf16_cfg<256, 256, 2, 4, 0, Epi, CAT, false, LEAD>(a, epi, s);
-            const int body = (rounds * NCU / tn) * 256;
-            // DYT_GEMM_ROWS_ONE_LAUNCH=1: both tile shapes in one launch (gemm_bf16_rows_kernel).  Measured: serial step 29.48 -> 28.92 ms
-            // (no second launch, no empty tail launches of compacted GEMMs), but the overlapped step 26.2-26.4 -> 26.7 ms: the tail
-            // workgroups then hold 128 KB of LDS like the big ones and keep the other pass's 64 KB kernels off their CUs.  Off.
-            static const bool one_launch = getenv("DYT_GEMM_ROWS_ONE_LAUNCH") && atoi(getenv("DYT_GEMM_ROWS_ONE_LAUNCH"));
-            if constexpr (LEAD == 0) { if (one_launch) return launch_bf16_rows<Epi, CAT>(a, epi, s, body); }
-            int rc = launch_bf16_cfg<256, 256, 2, 4, 0, Epi, CAT, false, LEAD>(a, epi, s, 0, body);
-            if (rc) return rc;
-            return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, CAT, false, LEAD>(a, epi, s, body, a.M);
-        }
-    }
-    if (a.N % 128 == 0) return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, CAT, false, LEAD>(a, epi, s);
-    if constexpr (!CAT && LEAD == 0) { if (a.N % 64 == 0) return launch_bf16_cfg<128, 64, 2, 2, 0>(a, epi, s); }
-    set_error("gemm_bf16: N=%d must be a multiple of 64", a.N);
+static int route_error(const GemmRoute& r, const GemmArgs& a) {
+    set_error("%s (M=%d N=%d K=%d)", r.error ? r.error : "gemm: this epilogue has no kernel of the routed family", a.M, a.N, a.K);
     return -1;
+}
+
+// the 16-bit MFMA kernels.  CAT / LEAD: a second operand pair in front of the contraction; F8: the "fp16f8" split contraction
+// (a.K = 2 x the logical K: K / 64 f16 tiles + K / 64 fp8 tiles)
+template <class Epi, bool CAT = false, int LEAD = 0, bool F8 = false>
+static int run_bf16(const GemmArgs& a, const Epi& epi, hipStream_t s) {
+    constexpr bool PLAIN = !CAT && LEAD == 0 && !F8;
+    const GemmRoute r = gemm_route(route_shape(a, F8 ? GF_F8 : GF_16, CAT, LEAD > 0, std::is_same<Epi, EpiStoreAT<bf16>>::value, SplitKEpi<Epi>::value));
+    switch (r.kernel) {
+        case GK_SPLITK:
+            if constexpr (SplitKEpi<Epi>::value && !F8) {
+                const int slices = splitk_slices(a.K, CAT);
+                hipLaunchKernelGGL((gemm_splitk_kernel<CAT>), dim3(a.N / 32, (a.M + 127) / 128, slices), dim3(256), 0, s, static_cast<const bf16*>(a.A),
+                                   static_cast<const bf16*>(a.W), a.M, a.N, a.K, a.a_map, static_cast<const bf16*>(a.A2), static_cast<const bf16*>(a.W2),
+                                   a.a2_map, a.splitk_ws);   // (not counted in g_bf16_kernel_launches: tools/pmc_traffic.py selects the gemm_bf16_* kernels)
+                hipLaunchKernelGGL((splitk_reduce_kernel<Epi>), dim3((unsigned)(((size_t)a.M * (a.N / 4) + 255) / 256)), dim3(256), 0, s, a.splitk_ws, slices, a.M,
+                                   a.N, a.out_scale, epi);
+                DYT_HIP_CHECK(hipGetLastError());
+                return 0;
+            }
+            break;
+        case GK_BPRE:
+            if constexpr (PLAIN) {
+                GemmArgs b = a; b.W = a.Wp;
+                return launch_bf16_bpre<0>(b, epi, s);
+            }
+            break;
+        case GK_256: {   // two launches on the same stream when the whole-rounds scheme leaves a tail; a compacted GEMM (device-side row count) leaves it empty
+            const int rc = launch_bf16_cfg<256, 256, 2, 4, 0, Epi, CAT, F8, LEAD>(a, epi, s, 0, r.body);
+            if (rc || r.body >= a.M) return rc;
+            return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, CAT, F8, LEAD>(a, epi, s, r.body, a.M);
+        }
+        case GK_128: return launch_bf16_cfg<128, 128, 2, 2, 0, Epi, CAT, F8, LEAD>(a, epi, s);
+        case GK_128x64:
+            if constexpr (PLAIN) return launch_bf16_cfg<128, 64, 2, 2, 0>(a, epi, s);
+            break;
+        default: break;
+    }
+    return route_error(r, a);
 }
 
 template <int BM, int BN, class Epi>
 static int launch_f32_cfg(const GemmArgs& a, const Epi& epi, hipStream_t s) {
-    const int grid = ((a.M + BM - 1) / BM) * (a.N / BN);
+    const int grid = tile_grid(0, a.M, a.N, BM, BN);
     const size_t lds = 2 * (BM + BN) * 128;
     auto kern = gemm_f32_mfma_nt_kernel<BM, BN, 2, 2, Epi>;
     static bool attr_set[64] = {};
@@ -1333,12 +1230,12 @@ static int launch_f32_cfg(const GemmArgs& a, const Epi& epi, hipStream_t s) {
 
 template <class Epi>
 static int run_f32(const GemmArgs& a, const Epi& epi, hipStream_t s) {
-    if (a.K % 64 != 0 || a.N % 64 != 0 || a.M <= 0) {
-        set_error("gemm_f32: N=%d %% 64, K=%d %% 64 required, M=%d", a.N, a.K, a.M);
-        return -1;
+    const GemmRoute r = gemm_route(route_shape(a, GF_F32));
+    switch (r.kernel) {
+        case GK_F32_128: return launch_f32_cfg<128, 128>(a, epi, s);
+        case GK_F32_128x64: return launch_f32_cfg<128, 64>(a, epi, s);
+        default: return route_error(r, a);
     }
-    if (a.N % 128 == 0) return launch_f32_cfg<128, 128>(a, epi, s);
-    return launch_f32_cfg<128, 64>(a, epi, s);
 }
 
 // epilogues of the forward GEMMs against frozen weights: the ones the fp8-correction kernels are built for
@@ -1354,7 +1251,7 @@ template <> struct F8Epi<EpiBiasF32> : std::true_type {};       // unit entry dy
 // SPLIT: fp32 epilogue functors on the 16-bit MFMA kernels (the fp32 operands arrive as K-concatenated 16-bit hi / lo parts)
 template <class AT, bool SPLIT, class Epi, int LEAD = 0>
 static int run(const GemmArgs& a, const Epi& epi, hipStream_t s) {
-    if constexpr (SPLIT && F8Epi<Epi>::value) { if (a.f8) return run_f8<Epi, LEAD>(a, epi, s); }
+    if constexpr (SPLIT && F8Epi<Epi>::value) { if (a.f8) return run_bf16<Epi, false, LEAD, true>(a, epi, s); }
     if (a.f8) { set_error("gemm: this epilogue has no fp8-correction form"); return -1; }
     if constexpr (sizeof(AT) == 2 || SPLIT) return run_bf16<Epi, false, LEAD>(a, epi, s);
     else return run_f32(a, epi, s);
@@ -1390,7 +1287,7 @@ static int dispatch(EpiKind kind, const GemmArgs& a, hipStream_t s) {
                 if (a.ln_part) {   // LayerNorm folded in
                     if (!a.ln_cs || !a.ln_st_out || !a.ln_scratch || a.K != LN_PARTS * 64) { set_error("gemm: folded LayerNorm form needs ln_cs, ln_st_out, ln_scratch and K = 768"); return -1; }
                     const float2* st = nullptr;
-                    if (!takes_bpre(a)) {   // no statistics prologue in these tile shapes: merge the partials in a pre-pass
+                    if (gemm_route(route_shape(a, GF_16)).kernel != GK_BPRE) {   // no statistics prologue in these tile shapes: merge the partials in a pre-pass
                         hipLaunchKernelGGL(ln_finalize_kernel, dim3((a.M + 255) / 256), dim3(256), 0, s, a.ln_part, a.a_map, a.a_map ? a.ln_scratch : a.ln_st_out,
                                            a.a_map ? a.ln_st_out : nullptr, a.M);
                         DYT_HIP_CHECK(hipGetLastError());

@@ -13,8 +13,7 @@
 
 namespace dyt {
 
-constexpr int SK_SLICE = 256;   // k per workgroup: 16 MFMA steps of 32x32x16
-constexpr int SK_MAX_M = 512;   // above this the 128x128 tiles fill enough CUs and the partials' round trip costs more than it saves
+// (SK_SLICE = 256, the k per workgroup, and SK_MAX_M: gemm_route.h)
 
 // k assignment inside a 64-wide block: lane half h = lane >> 5 takes k in [32 h, 32 h + 32), MFMA step s its chunk [8 s, 8 s + 8) -- the
 // same on both operands, so any assignment is a valid contraction order; this one makes a lane's four fragments of a block one 64-B run.

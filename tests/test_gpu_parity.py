@@ -219,6 +219,27 @@ def test_gemm_variants_full_occupancy_bitwise():
         assert float((outs[0].float() - ref).abs().max() / ref.abs().max()) < 1e-2
 
 
+def test_product_dispatch_route_boundaries_bitwise():
+    """The product dispatch (variant 30: csrc/gemm_route.h) at the thresholds of its routing -- M = 2047 / 2048 (128x128 tiles below, 256x256
+    above), 16128 / 16129 rows of N = 768 (189 / 192 tiles of 256x256: below / at 3/4 of a round of the 256 CUs) and 21761 rows (a 256x256 body
+    of whole rounds + a one-row 128x128 tail).  Every kernel accumulates in the same k order, so the bf16 output must be BITWISE that of
+    128x128 tiles everywhere (variant 0); both must match an fp32 reference."""
+    from _lib import check, lib, ptr, stream_ptr
+    for (M, N, K) in [(2047, 2304, 768), (2048, 2304, 768), (2048, 768, 768), (16128, 768, 3072), (16129, 768, 3072), (21761, 768, 3072)]:
+        g = torch.Generator(device="cuda").manual_seed(M + N)
+        a = torch.randn(M, K, device="cuda", generator=g).bfloat16()
+        w = (torch.randn(N, K, device="cuda", generator=g) * 0.05).bfloat16()
+        outs = []
+        for variant in (0, 30):
+            c = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
+            check(lib().dyt_gemm_bf16_raw(ptr(a), ptr(w), ptr(c), M, N, K, variant, stream_ptr()))
+            torch.cuda.synchronize()
+            outs.append(c)
+        assert torch.equal(outs[1], outs[0]), (M, N, K, int((outs[1] != outs[0]).sum()))
+        ref = a.float() @ w.float().t()
+        assert float((outs[0].float() - ref).abs().max() / ref.abs().max()) < 1e-2, (M, N, K)
+
+
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_scheduling_options_do_not_change_results(precision):
     """Stream overlap (1: the two passes on two HIP streams, 2: plus per-block adapter-branch streams), the cls-only tail
