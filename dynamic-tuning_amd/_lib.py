@@ -26,6 +26,8 @@ PREC_FP16X3Q = 7  # host-side name only: PREC_FP16X3H with the attention branch'
 PREC_FP16X3 = 3   # host-side name only: libdyt_hip_f16.so in its fp32 mode with DYT_OPT_F32_SPLIT16 (frozen-weight GEMMs as three IEEE-half products)
 F_TRAINING, F_COMPLETE, F_SAVE, F_MASKED_DENSE, F_GATE_ALWAYS, F_ACCUM_GRAD, F_DEVICE_SEED, F_TOKENS_IN, F_TOKENS_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256
 CREATE_WIDE_HEAD = 1   # dyt_ctx_create_ex: DYT_CREATE_WIDE_HEAD (the head on the MFMA kernels of csrc/head_wide.hip, up to 65 536 classes)
+CREATE_AVG_POOL = 2    # DYT_CREATE_AVG_POOL: global_pool='avg' -- the head reads the mean of the 196 patch rows (given together with CREATE_FC_NORM)
+CREATE_FC_NORM = 4     # DYT_CREATE_FC_NORM: the head's LayerNorm is the trainable fc_norm of the flat buffer, the final norm an identity
 OPT_STREAM_OVERLAP, OPT_CLS_TAIL, OPT_SHARE_BLOCK0, OPT_COUNT_FLOPS_TOKENS, OPT_GRAD_SCALE_LOG2, OPT_FC2_CAT, OPT_ATTN_BWD_FUSED, OPT_F32_SPLIT16, OPT_ATTN_V2, OPT_GEMM_SPLITK, OPT_LEARNABLE_SCALE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 
 # enum dyt_param (include/dyt_hip.h)
@@ -34,6 +36,9 @@ OPT_STREAM_OVERLAP, OPT_CLS_TAIL, OPT_SHARE_BLOCK0, OPT_COUNT_FLOPS_TOKENS, OPT_
  P_GATE_W, P_GATE_B, P_HEAD_W, P_HEAD_B,
  P_POOL_QUERY, P_POOL_NQ_W, P_POOL_NQ_B, P_POOL_NK_W, P_POOL_NK_B, P_POOL_NV_W, P_POOL_NV_B, P_POOL_Q_W, P_POOL_K_W,
  P_POOL_V_W, P_POOL_Q_BIAS, P_POOL_V_BIAS, P_POOL_PROJ_W, P_POOL_PROJ_B, P_AD_SCALE, P_AD_LN_W, P_AD_LN_B, P_COUNT) = range(44)
+# ABI v5: DYT_P_FC_NORM_W / _B, appended to the C enum in front of DYT_P_COUNT.  P_COUNT above stays the number of ids of a context created
+# WITHOUT DYT_CREATE_FC_NORM (every id a default model's keys map to lies below it); P_COUNT_ALL is the C enum's DYT_P_COUNT.
+P_FC_NORM_W, P_FC_NORM_B, P_COUNT_ALL = P_COUNT, P_COUNT + 1, P_COUNT + 2
 
 # reference state_dict key suffix -> param id  
 GLOBAL_KEYS = {
@@ -52,6 +57,8 @@ POOL_KEYS = {
     "attentive_blocks.cross_attn.proj.bias": P_POOL_PROJ_B,
 }
 GLOBAL_KEYS.update(POOL_KEYS)
+# only with global_pool='avg' / fc_norm=True (reference models/vision_transformer_IN21K.py:261,316): trainable, absent from the checkpoint
+GLOBAL_KEYS.update({"fc_norm.weight": P_FC_NORM_W, "fc_norm.bias": P_FC_NORM_B})
 BLOCK_KEYS = {
     "norm1.weight": P_LN1_W, "norm1.bias": P_LN1_B, "attn.qkv.weight": P_QKV_W, "attn.qkv.bias": P_QKV_B,
     "attn.proj.weight": P_PROJ_W, "attn.proj.bias": P_PROJ_B, "norm2.weight": P_LN2_W, "norm2.bias": P_LN2_B,
@@ -166,6 +173,7 @@ SYMBOLS = {
     "dyt_adapter_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _u64, _i, _vp]),
     "dyt_adapter_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _u64, _i, _vp]),
     "dyt_head_wide": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "dyt_pool_head": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_uint32, _vp]),
     "dyt_mlp_gathered_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "dyt_mlp_gathered_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "dyt_gate_compact": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -139,14 +139,21 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
         int rc = pool_backward(c, S, trainable, dlogits, grad, s);
         if (rc) return rc;
     } else {
+        // (the head's input rows and LayerNorm as in forward_impl; under DYT_CREATE_AVG_POOL the head leaves dpooled in its compact form
+        // and avg_pool_bwd is the one writer of the gradient stream)
+        const float* hx = c->avg_pool ? S.pooled : S.xs[depth]; const size_t hx_stride = c->avg_pool ? (size_t)D : (size_t)NT * D;
+        const float* hnw = c->fc_norm ? trainable + c->off_fnw : c->norm_w;
+        const bool compact = cls_tail || c->avg_pool;
         if (c->wide_head)
-            RUN(2, 0, launch_head_wide_bwd(dlogits, S.xs[depth], (size_t)NT * D, S.cls_n, S.head_stats, c->norm_w, trainable + c->off_hw,
-                                           cls_tail ? S.gcls : g, grad + c->off_hw, grad + c->off_hb, B, c->cfg.num_classes,
-                                           cls_tail ? 1 : 0, S.head_part, s));
+            RUN(2, 0, launch_head_wide_bwd(dlogits, hx, hx_stride, S.cls_n, S.head_stats, hnw, trainable + c->off_hw,
+                                           compact ? S.gcls : g, grad + c->off_hw, grad + c->off_hb, B, c->cfg.num_classes,
+                                           compact ? 1 : 0, S.head_part, s, S.head_dy));
         else
-        RUN(2, 0, launch_head_bwd(dlogits, S.xs[depth], S.cls_n, S.head_stats, c->norm_w, trainable + c->off_hw,
-                                  cls_tail ? S.gcls : g, grad + c->off_hw, grad + c->off_hb, B, c->cfg.num_classes,
-                                  cls_tail ? 1 : 0, s));
+        RUN(2, 0, launch_head_bwd(dlogits, hx, S.cls_n, S.head_stats, hnw, trainable + c->off_hw,
+                                  compact ? S.gcls : g, grad + c->off_hw, grad + c->off_hb, B, c->cfg.num_classes,
+                                  compact ? 1 : 0, s, hx_stride, S.head_dy));
+        if (c->fc_norm) RUN(2, 0, launch_fc_norm_param_grad(S.head_dy, hx, hx_stride, S.head_stats, grad + c->off_fnw, grad + c->off_fnb, B, s));
+        if (c->avg_pool) RUN(2, 0, launch_avg_pool_bwd(S.gcls, g, B, s));
         { const int l = depth; CK("head_bwd g", cls_tail ? S.gcls : g, (size_t)(cls_tail ? B : M) * D * 4); CK("head_bwd dW", grad + c->off_hw, (size_t)c->cfg.num_classes * D * 4); }
     }
 

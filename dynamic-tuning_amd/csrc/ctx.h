@@ -104,6 +104,8 @@ struct Slot {
     float* gcls = nullptr;   // last block backward: gradient at the cls rows [B,768]
     float* cls_n = nullptr;
     float2* head_stats = nullptr;
+    float* pooled = nullptr;      // dyt_ctx::avg_pool: [max_batch][768] the head's input rows (avg_pool_fwd)
+    float* head_dy = nullptr;     // dyt_ctx::fc_norm, training layout: [max_batch][768] dlogits @ W_head, the gradient behind fc_norm (its parameter gradients)
     float* head_part = nullptr;   // dyt_ctx::wide_head, training layout: [ceil(C/1024)][max_batch][768] class-slice partial sums of the head's dx (per slot: the two passes' backward run on two streams)
     int batch = 0, flags = 0;
     bool valid = false;
@@ -124,6 +126,11 @@ struct dyt_ctx {
     // DYT_CREATE_WIDE_HEAD (dyt_ctx_create_ex): the head runs on the MFMA kernels of head_wide.hip (num_classes up to 65 536) instead of the row
     // kernels of rowops.hip (up to 1024, the bit-pinned default); image model only
     bool wide_head = false;
+    // DYT_CREATE_FC_NORM: the head's LayerNorm is the reference's fc_norm -- gamma / beta are trainable words of the caller's flat buffer
+    // (off_fnw / off_fnb, directly behind head.bias) and the frozen norm_w / norm_b are not used; DYT_CREATE_AVG_POOL (given with DYT_CREATE_FC_NORM only): the row
+    // that LayerNorm reads is the mean of the 196 patch rows of the last block's output (Slot::pooled) instead of the cls row; no cls-only tail
+    bool fc_norm = false, avg_pool = false;
+    int64_t off_fnw = 0, off_fnb = 0;
     int prec;
     size_t at;  // bytes per activation element
     char* arena = nullptr;

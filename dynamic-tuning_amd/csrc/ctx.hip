@@ -89,6 +89,8 @@ static void layout(dyt_ctx* c, bool dry) {
         S.cls_n = carve<float>(c, B * D, dry);
         S.head_stats = carve<float2>(c, B, dry);
         if (c->wide_head) S.head_part = bwd_f32(head_wide_scratch_floats((int)B, (int)C));
+        if (c->avg_pool) S.pooled = carve<float>(c, B * D, dry);
+        if (c->fc_norm) S.head_dy = bwd_f32(B * D);
         for (size_t l = 0; l < depth; ++l) {
             LayerS& L = S.L[l];
             if (inf && l > 0) { L = S.L[0]; continue; }   // one set of per-block buffers: every block's launches run in stream order, each rewrites what it reads
@@ -293,6 +295,7 @@ static void trainable_layout(dyt_ctx* c) {
     o = c->layer_stride * c->cfg.depth;
     c->off_hw = o; o = a4(o + C * D);
     c->off_hb = o; o = a4(o + C);
+    if (c->fc_norm) { c->off_fnw = o; o += D; c->off_fnb = o; o += D; }   // fc_norm gamma / beta directly behind head.bias (inside part 0 of dyt_grad_part)
     if (c->frames > 1) {
         c->off_pquery = o; o += D;
         c->off_pnq_w = o; o += D; c->off_pnq_b = o; o += D;
@@ -309,7 +312,7 @@ static void trainable_layout(dyt_ctx* c) {
 }
 
 extern "C" const char* dyt_last_error(void) { return g_err; }
-extern "C" int dyt_version(void) { return 4; }   // 2: dyt_config::adapter_ln appended (round 6); 3: dyt_config::inference_only appended; 4: dyt_ctx_create_ex, dyt_head_wide
+extern "C" int dyt_version(void) { return 5; }   // 2: dyt_config::adapter_ln appended (round 6); 3: dyt_config::inference_only appended; 4: dyt_ctx_create_ex, dyt_head_wide; 5: DYT_CREATE_AVG_POOL / _FC_NORM, dyt_pool_head
 
 // dyt_config::inference_only: the entry points that need what such a context does not carve refuse before anything is enqueued
 int dyt::refuse_inference(const dyt_ctx* c, const char* what) {
@@ -330,8 +333,23 @@ extern "C" int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out) { return dyt
 
 extern "C" int dyt_ctx_create_ex(const dyt_config* cfg, uint32_t create_flags, dyt_ctx** out) {
     if (!cfg || !out) { set_error("null argument"); return DYT_ERR_ARG; }
-    if (create_flags & ~DYT_CREATE_WIDE_HEAD) { set_error("dyt_ctx_create_ex: unknown create_flags 0x%x (known: DYT_CREATE_WIDE_HEAD = 0x%x)", create_flags, DYT_CREATE_WIDE_HEAD); return DYT_ERR_ARG; }
+    const uint32_t known_flags = DYT_CREATE_WIDE_HEAD | DYT_CREATE_AVG_POOL | DYT_CREATE_FC_NORM;
+    if (create_flags & ~known_flags) {
+        set_error("dyt_ctx_create_ex: unknown create_flags 0x%x (known: DYT_CREATE_WIDE_HEAD = 0x%x, DYT_CREATE_AVG_POOL = 0x%x, DYT_CREATE_FC_NORM = 0x%x)",
+                  create_flags, DYT_CREATE_WIDE_HEAD, DYT_CREATE_AVG_POOL, DYT_CREATE_FC_NORM);
+        return DYT_ERR_ARG;
+    }
     const bool wide = (create_flags & DYT_CREATE_WIDE_HEAD) != 0;
+    const bool avg_pool = (create_flags & DYT_CREATE_AVG_POOL) != 0, fc_norm = (create_flags & DYT_CREATE_FC_NORM) != 0;
+    if (avg_pool && !fc_norm) {   // the reference's ('avg', fc_norm=False): LayerNorm over all 197 rows in front of the mean, a frozen norm -- no HIP path
+        set_error("dyt_ctx_create_ex: create_flags 0x%x: DYT_CREATE_AVG_POOL without DYT_CREATE_FC_NORM (global_pool='avg' with fc_norm=False) is not "
+                  "implemented; pass both bits (0x%x)", create_flags, DYT_CREATE_AVG_POOL | DYT_CREATE_FC_NORM);
+        return DYT_ERR_ARG;
+    }
+    if (fc_norm && cfg->frames > 1) {
+        set_error("%s: image model only (frames=%d: the video model has its own attentive pooling head)", avg_pool ? "DYT_CREATE_AVG_POOL" : "DYT_CREATE_FC_NORM", cfg->frames);
+        return DYT_ERR_ARG;
+    }
     if (wide && cfg->num_classes > 65536) {
         set_error("unsupported config: num_classes=%d (1..65536 with DYT_CREATE_WIDE_HEAD; 1..1024 without)", cfg->num_classes);
         return DYT_ERR_ARG;
@@ -360,11 +378,13 @@ extern "C" int dyt_ctx_create_ex(const dyt_config* cfg, uint32_t create_flags, d
     c->cfg = *cfg;
     c->inf = cfg->inference_only != 0;
     c->wide_head = wide;
+    c->fc_norm = fc_norm; c->avg_pool = avg_pool;
     c->prec = cfg->precision;
     c->frames = cfg->frames > 1 ? cfg->frames : 1;
     c->ad_ln = cfg->adapter_ln;
     if (c->frames > 1) c->cls_tail = false;   // every token of the last block reaches the pooling head
     if (c->ad_ln) c->cls_tail = false;        // (generic path: the adapter's LayerNorm runs over all rows of every block)
+    if (c->avg_pool) c->cls_tail = false;     // every patch token of the last block reaches the head
     c->at = at_size(c->prec);
 #ifdef DYT_FP16
     if (c->prec != DYT_PREC_FP32) c->gs = 4096.0f;
@@ -458,6 +478,9 @@ extern "C" int dyt_trainable_offset(const dyt_ctx* c, int param, int layer, int6
             *off = base + (param == DYT_P_AD_LN_W ? c->off_alw : c->off_alb); *numel = D; break;
         case DYT_P_HEAD_W: *off = c->off_hw; *numel = C * D; break;
         case DYT_P_HEAD_B: *off = c->off_hb; *numel = C; break;
+        case DYT_P_FC_NORM_W: case DYT_P_FC_NORM_B:
+            if (!c->fc_norm) { set_error("param %d exists with DYT_CREATE_FC_NORM / DYT_CREATE_AVG_POOL only", param); return DYT_ERR_ARG; }
+            *off = param == DYT_P_FC_NORM_W ? c->off_fnw : c->off_fnb; *numel = D; break;
         case DYT_P_POOL_QUERY: case DYT_P_POOL_NQ_W: case DYT_P_POOL_NQ_B: case DYT_P_POOL_NK_W: case DYT_P_POOL_NK_B:
         case DYT_P_POOL_NV_W: case DYT_P_POOL_NV_B: case DYT_P_POOL_Q_W: case DYT_P_POOL_K_W: case DYT_P_POOL_V_W:
         case DYT_P_POOL_Q_BIAS: case DYT_P_POOL_V_BIAS: case DYT_P_POOL_PROJ_W: case DYT_P_POOL_PROJ_B: {
@@ -551,6 +574,11 @@ extern "C" int dyt_set_frozen(dyt_ctx* c, int param, int layer, const float* src
 }
 static int set_frozen_impl(dyt_ctx* c, int param, int layer, const float* src, void* stream) {
     if (!c || !src) { set_error("null argument"); return DYT_ERR_ARG; }
+    if (c->fc_norm && (param == DYT_P_NORM_W || param == DYT_P_NORM_B)) {
+        set_error("DYT_P_NORM_%s: the context was created with DYT_CREATE_FC_NORM (the final norm is an identity there; the head's LayerNorm is the "
+                  "trainable DYT_P_FC_NORM_W / _B of the flat buffer)", param == DYT_P_NORM_W ? "W" : "B");
+        return DYT_ERR_ARG;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool per_layer = param >= DYT_P_LN1_W && param <= DYT_P_FC2_B;
     if (per_layer && (layer < 0 || layer >= c->cfg.depth)) { set_error("layer %d out of range", layer); return DYT_ERR_ARG; }
@@ -618,7 +646,7 @@ extern "C" int dyt_ctx_set_option(dyt_ctx* c, int option, int value) {
             c->overlap = value != 0; c->ov_pass = value == 1 || value == 2 || value == 4; c->ov_branch = value == 2 || value == 3;
             c->ov_bwd_serial = value == 4;
             return DYT_OK;
-        case DYT_OPT_CLS_TAIL: c->cls_tail = value != 0 && c->frames <= 1 && !c->ad_ln; for (auto& S : c->slots) S.valid = false; return DYT_OK;
+        case DYT_OPT_CLS_TAIL: c->cls_tail = value != 0 && c->frames <= 1 && !c->ad_ln && !c->avg_pool; for (auto& S : c->slots) S.valid = false; return DYT_OK;
         case DYT_OPT_SHARE_BLOCK0: c->share_block0 = value != 0; return DYT_OK;
         case DYT_OPT_GRAD_SCALE_LOG2:   // 16-bit gradient operands carry 2^value (0 = none); fp32 mode ignores it
             if (value < 0 || value > 24) { set_error("grad scale log2 %d out of range 0..24", value); return DYT_ERR_ARG; }

@@ -406,12 +406,18 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     } else if (c->frames > 1) {
         int rc = pool_forward(c, S, trainable, logits, B, s);
         if (rc) return rc;
-    } else if (c->wide_head) {
-        RUN(2, 0, launch_head_wide_fwd(S.xs[depth], (size_t)NT * D, c->norm_w, c->norm_b, trainable + c->off_hw, trainable + c->off_hb, S.cls_n,
-                                       S.head_stats, logits, B, c->cfg.num_classes, s));
     } else {
-        RUN(2, 0, launch_head_fwd(S.xs[depth], c->norm_w, c->norm_b, trainable + c->off_hw, trainable + c->off_hb, S.cls_n,
-                                  S.head_stats, logits, B, c->cfg.num_classes, s));
+        // the head's input row per image and its LayerNorm: the cls row and the frozen final norm, or -- DYT_CREATE_FC_NORM -- the trainable
+        // fc_norm of the flat buffer, on -- DYT_CREATE_AVG_POOL -- the mean of the patch rows (reference :375-380)
+        const float* hx = S.xs[depth]; size_t hx_stride = (size_t)NT * D;
+        if (c->avg_pool) { RUN(2, 0, launch_avg_pool_fwd(S.xs[depth], S.pooled, B, s)); hx = S.pooled; hx_stride = D; }
+        const float* hnw = c->fc_norm ? trainable + c->off_fnw : c->norm_w; const float* hnb = c->fc_norm ? trainable + c->off_fnb : c->norm_b;
+        if (c->wide_head)
+            RUN(2, 0, launch_head_wide_fwd(hx, hx_stride, hnw, hnb, trainable + c->off_hw, trainable + c->off_hb, S.cls_n,
+                                           S.head_stats, logits, B, c->cfg.num_classes, s));
+        else
+            RUN(2, 0, launch_head_fwd(hx, hnw, hnb, trainable + c->off_hw, trainable + c->off_hb, S.cls_n,
+                                      S.head_stats, logits, B, c->cfg.num_classes, s, hx_stride));
     }
     c->pass_ran = true;
     S.batch = B; S.flags = flags; S.valid = save && !tokens_in && !tokens_out; S.trainable = trainable; S.saved16 = save16;   // token-level passes are forward only

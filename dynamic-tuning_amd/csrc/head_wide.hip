@@ -198,7 +198,8 @@ __global__ __launch_bounds__(256) void head_wide_dx_kernel(const float* __restri
 __global__ __launch_bounds__(256) void head_wide_dx_finish_kernel(const float* __restrict__ part, int nslices,
                                                                   const float* __restrict__ x, size_t x_stride,
                                                                   const float2* __restrict__ stats, const float* __restrict__ nw,
-                                                                  float* __restrict__ g, size_t g_stride, int B) {
+                                                                  float* __restrict__ g, size_t g_stride, int B,
+                                                                  float* __restrict__ dy_out) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float2 st = stats[b];
@@ -209,6 +210,7 @@ __global__ __launch_bounds__(256) void head_wide_dx_finish_kernel(const float* _
         const int ch = tid + 256 * i;
         float acc = part[(size_t)b * D + ch];
         for (int s = 1; s < nslices; ++s) acc += part[((size_t)s * B + b) * D + ch];
+        if (dy_out) dy_out[(size_t)b * D + ch] = acc;   // the gradient behind the LayerNorm (a trainable fc_norm's parameter gradients)
         xh[i] = (x[(size_t)b * x_stride + ch] - st.x) * st.y;
         dy[i] = acc * nw[ch];
         s1 += dy[i];
@@ -316,7 +318,7 @@ int launch_head_wide_fwd(const float* x, size_t x_stride, const float* nw, const
 
 int launch_head_wide_bwd(const float* dlogits, const float* x, size_t x_stride, const float* cls_n, const float2* stats,
                          const float* nw, const float* hw, float* g, float* dWh, float* dbh, int batch, int C, int compact,
-                         float* part, hipStream_t s) {
+                         float* part, hipStream_t s, float* dy_out) {
     if (head_wide_args("head_wide_bwd", batch, C)) return -1;
     if (g) {
         if (!part) { set_error("head_wide_bwd: no slice scratch"); return -1; }
@@ -324,7 +326,7 @@ int launch_head_wide_bwd(const float* dlogits, const float* x, size_t x_stride, 
         hipLaunchKernelGGL(head_wide_dx_kernel, dim3(D / BN, ceil_div(batch, BM), n_slices(C)), dim3(THREADS), 0, s, dlogits, hw, part,
                            batch, C);
         hipLaunchKernelGGL(head_wide_dx_finish_kernel, dim3(batch), dim3(256), 0, s, part, n_slices(C), x, x_stride, stats, nw, g,
-                           compact ? (size_t)D : (size_t)NT * D, batch);
+                           compact ? (size_t)D : (size_t)NT * D, batch, dy_out);
     }
     if (dWh || dbh)
         hipLaunchKernelGGL(head_wide_dw_kernel, dim3(D / BN, ceil_div(C, BM)), dim3(THREADS), 0, s, dlogits, cls_n, dWh, dbh, batch, C);

@@ -211,12 +211,14 @@ int launch_pad_convert(int precision, const float* src, void* dst, int rows, int
                        int dst_cols, hipStream_t s);
 
 // head: final LayerNorm on the cls rows + Linear(768, C)
+// (x row b at x + b * x_stride: the cls rows of the token stream by default, the [B,768] pooled rows under DYT_CREATE_AVG_POOL)
 int launch_head_fwd(const float* x, const float* nw, const float* nb, const float* hw, const float* hb,
-                    float* cls_n, float2* stats, float* logits, int batch, int C, hipStream_t s);
+                    float* cls_n, float2* stats, float* logits, int batch, int C, hipStream_t s, size_t x_stride = (size_t)NT * D);
 // g (all rows) = 0 except cls rows = LNbwd(dlogits @ Wh); dWh += dlogits^T cls_n ; dbh += colsum(dlogits)
 int launch_head_bwd(const float* dlogits, const float* x, const float* cls_n, const float2* stats,
                     const float* nw, const float* hw, float* g, float* dWh, float* dbh, int batch, int C,
-                    int compact, hipStream_t s);  // compact: g is [B,768] (cls rows only), no zero fill
+                    int compact, hipStream_t s,   // compact: g is [B,768] (cls rows only), no zero fill
+                    size_t x_stride = (size_t)NT * D, float* dy_out = nullptr);   // dy_out [B,768]: + dlogits @ Wh, the gradient behind the LayerNorm (fc_norm's parameter gradients)
 // The same head for up to 65 536 classes on exact-fp32 MFMA kernels (head_wide.hip, DYT_CREATE_WIDE_HEAD): another summation order
 // than the row kernels above, so a separate form.  x row b at x + b * x_stride; part = head_wide_scratch_floats(batch, C) floats
 // ([ceil(C/1024) class slices][batch][768] partial sums of dx); g / dWh / dbh may each be null (not computed).
@@ -225,7 +227,15 @@ int launch_head_wide_fwd(const float* x, size_t x_stride, const float* nw, const
                          float* cls_n, float2* stats, float* logits, int batch, int C, hipStream_t s);
 int launch_head_wide_bwd(const float* dlogits, const float* x, size_t x_stride, const float* cls_n, const float2* stats,
                          const float* nw, const float* hw, float* g, float* dWh, float* dbh, int batch, int C, int compact,
-                         float* part, hipStream_t s);
+                         float* part, hipStream_t s, float* dy_out = nullptr);   // dy_out: as launch_head_bwd
+
+// Mean-pooled head (pool_avg.hip, DYT_CREATE_AVG_POOL / DYT_CREATE_FC_NORM).  pooled [B,768] = mean of the 196 patch rows of x [B,197,768];
+// its backward writes the whole gradient stream g [B,197,768] (cls rows 0, patch rows dpooled / 196); the head LayerNorm's parameter
+// gradients d_gamma[c] += sum_b dy[b][c] xhat[b][c], d_beta[c] += sum_b dy[b][c] in ascending image order (xhat recomputed from x and stats)
+int launch_avg_pool_fwd(const float* x, float* pooled, int batch, hipStream_t s);
+int launch_avg_pool_bwd(const float* dpooled, float* g, int batch, hipStream_t s);
+int launch_fc_norm_param_grad(const float* dy, const float* x, size_t x_stride, const float2* stats, float* d_gamma, float* d_beta,
+                              int batch, hipStream_t s);
 
 struct LossArgs {
     const float* logits_s; const float* logits_t; const int64_t* targets;

@@ -608,11 +608,12 @@ int launch_pad_convert(int precision, const float* src, void* dst, int rows, int
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ nw,
                                                        const float* __restrict__ nb, const float* __restrict__ hw,
                                                        const float* __restrict__ hb, float* __restrict__ cls_n,
-                                                       float2* __restrict__ stats, float* __restrict__ logits, int C) {
+                                                       float2* __restrict__ stats, float* __restrict__ logits, int C,
+                                                       size_t x_stride) {
     __shared__ float row[D];
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* xp = x + (size_t)b * NT * D;
+    const float* xp = x + (size_t)b * x_stride;
     float v[3];
     float s = 0.f;
 #pragma unroll
@@ -641,8 +642,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
     }
 }
 int launch_head_fwd(const float* x, const float* nw, const float* nb, const float* hw, const float* hb, float* cls_n,
-                    float2* stats, float* logits, int batch, int C, hipStream_t s) {
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(batch), dim3(256), 0, s, x, nw, nb, hw, hb, cls_n, stats, logits, C);
+                    float2* stats, float* logits, int batch, int C, hipStream_t s, size_t x_stride) {
+    hipLaunchKernelGGL(head_fwd_kernel, dim3(batch), dim3(256), 0, s, x, nw, nb, hw, hb, cls_n, stats, logits, C, x_stride);
     LAUNCH_CHECK();
     return 0;
 }
@@ -650,7 +651,7 @@ int launch_head_fwd(const float* x, const float* nw, const float* nb, const floa
 __global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restrict__ dlogits, const float* __restrict__ x,
                                                           const float2* __restrict__ stats, const float* __restrict__ nw,
                                                           const float* __restrict__ hw, float* __restrict__ g, int C,
-                                                          int g_stride) {
+                                                          int g_stride, size_t x_stride, float* __restrict__ dy_out) {
     __shared__ float red[4];
     __shared__ float dl[1024];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -665,7 +666,8 @@ __global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restric
         float acc = 0.f;
 #pragma unroll 8
         for (int c = 0; c < C; ++c) acc = fmaf(dl[c], hw[(size_t)c * D + ch], acc);
-        xh[i] = (x[(size_t)b * NT * D + ch] - st.x) * st.y;
+        if (dy_out) dy_out[(size_t)b * D + ch] = acc;   // the gradient behind the LayerNorm (a trainable fc_norm's parameter gradients)
+        xh[i] = (x[(size_t)b * x_stride + ch] - st.x) * st.y;
         dy[i] = acc * nw[ch];
         s1 += dy[i];
         s2 = fmaf(dy[i], xh[i], s2);
@@ -712,16 +714,17 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const float* __restric
         }
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) dW[(size_t)c * D + tid + 256 * i] += acc[i];
-    if (tid == 0) db[c] += sb;
+    for (int i = 0; i < 3; ++i) if (dW) dW[(size_t)c * D + tid + 256 * i] += acc[i];   // (either may be null: dyt_pool_head)
+    if (tid == 0 && db) db[c] += sb;
 }
 int launch_head_bwd(const float* dlogits, const float* x, const float* cls_n, const float2* stats, const float* nw,
-                    const float* hw, float* g, float* dWh, float* dbh, int batch, int C, int compact, hipStream_t s) {
+                    const float* hw, float* g, float* dWh, float* dbh, int batch, int C, int compact, hipStream_t s,
+                    size_t x_stride, float* dy_out) {
     if (C > 1024) { set_error("head_bwd: num_classes %d > 1024 unsupported", C); return -1; }
     if (!compact) DYT_HIP_CHECK(hipMemsetAsync(g, 0, (size_t)batch * NT * D * sizeof(float), s));
     hipLaunchKernelGGL(head_bwd_dx_kernel, dim3(batch), dim3(256), 0, s, dlogits, x, stats, nw, hw, g, C,
-                       compact ? D : NT * D);
-    hipLaunchKernelGGL(head_bwd_dw_kernel, dim3(C), dim3(256), 0, s, dlogits, cls_n, dWh, dbh, batch, C);
+                       compact ? D : NT * D, x_stride, dy_out);
+    if (dWh || dbh) hipLaunchKernelGGL(head_bwd_dw_kernel, dim3(C), dim3(256), 0, s, dlogits, cls_n, dWh, dbh, batch, C);
     LAUNCH_CHECK();
     return 0;
 }

@@ -351,6 +351,49 @@ extern "C" int dyt_head_wide(const float* cls_x, const float* norm_w, const floa
     return DYT_OK;
 }
 
+// The pooled head alone (pool_avg.hip + the head kernels): the launches of forward_impl / backward_impl under DYT_CREATE_AVG_POOL /
+// DYT_CREATE_FC_NORM (row-kernel or wide head), on caller-supplied tokens.
+extern "C" int dyt_pool_head(const float* x_tokens, const float* fc_norm_w, const float* fc_norm_b, const float* head_w, const float* head_b,
+                             float* logits, const float* dlogits, float* dx_tokens, float* d_fc_norm_w, float* d_fc_norm_b,
+                             float* d_head_w, float* d_head_b, int batch, int C, uint32_t create_flags, void* stream) {
+    const bool wide = (create_flags & DYT_CREATE_WIDE_HEAD) != 0, avg = (create_flags & DYT_CREATE_AVG_POOL) != 0;
+    if ((create_flags & ~(DYT_CREATE_WIDE_HEAD | DYT_CREATE_AVG_POOL | DYT_CREATE_FC_NORM)) || !(create_flags & DYT_CREATE_FC_NORM)) {
+        set_error("dyt_pool_head: create_flags 0x%x (DYT_CREATE_FC_NORM, optionally with DYT_CREATE_AVG_POOL and DYT_CREATE_WIDE_HEAD)", create_flags);
+        return DYT_ERR_ARG;
+    }
+    if (!x_tokens || !fc_norm_w || !fc_norm_b || !head_w || !head_b || !logits || (dlogits && !dx_tokens) || batch < 1 || C < 1 || C > (wide ? 65536 : 1024)) {
+        set_error("dyt_pool_head: bad argument (batch %d, C %d: 1..%d)", batch, C, wide ? 65536 : 1024);
+        return DYT_ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    float* cls_n = (float*)sc.get((size_t)batch * D * 4);
+    float2* stats = (float2*)sc.get((size_t)batch * sizeof(float2));
+    float* pooled = avg ? (float*)sc.get((size_t)batch * D * 4) : nullptr;
+    float* dy = dlogits ? (float*)sc.get((size_t)batch * D * 4) : nullptr;
+    float* dpooled = dlogits && avg ? (float*)sc.get((size_t)batch * D * 4) : nullptr;
+    float* part = dlogits && wide ? (float*)sc.get(head_wide_scratch_floats(batch, C) * 4) : nullptr;
+    if (!cls_n || !stats || (avg && !pooled) || (dlogits && !dy) || (dlogits && avg && !dpooled) || (dlogits && wide && !part)) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+    const float* hx = x_tokens; size_t hx_stride = (size_t)NT * D;
+    int rc = 0;
+    if (avg) { rc = launch_avg_pool_fwd(x_tokens, pooled, batch, s); if (rc) return rc; hx = pooled; hx_stride = D; }
+    rc = wide ? launch_head_wide_fwd(hx, hx_stride, fc_norm_w, fc_norm_b, head_w, head_b, cls_n, stats, logits, batch, C, s)
+              : launch_head_fwd(hx, fc_norm_w, fc_norm_b, head_w, head_b, cls_n, stats, logits, batch, C, s, hx_stride);
+    if (rc) return rc;
+    if (dlogits) {
+        float* g = avg ? dpooled : dx_tokens;
+        const int compact = avg ? 1 : 0;
+        rc = wide ? launch_head_wide_bwd(dlogits, hx, hx_stride, cls_n, stats, fc_norm_w, head_w, g, d_head_w, d_head_b, batch, C, compact, part, s, dy)
+                  : launch_head_bwd(dlogits, hx, cls_n, stats, fc_norm_w, head_w, g, d_head_w, d_head_b, batch, C, compact, s, hx_stride, dy);
+        if (rc) return rc;
+        rc = launch_fc_norm_param_grad(dy, hx, hx_stride, stats, d_fc_norm_w, d_fc_norm_b, batch, s);
+        if (rc) return rc;
+        if (avg) { rc = launch_avg_pool_bwd(dpooled, dx_tokens, batch, s); if (rc) return rc; }
+    }
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
 // The token-gathered MLP of block `layer` with the context's frozen weights (reference models/model_speed_test.py:297-305):
 // x [B*197,768] += scatter(fc2(gelu(fc1(LN2(gather(u, mask)))))) for the tokens whose mask is non-zero; u, x fp32, mask [B*197].
 extern "C" int dyt_mlp_gathered_fwd(dyt_ctx* c, int layer, const float* u, const float* mask, float* x, int batch, int32_t* total_out,

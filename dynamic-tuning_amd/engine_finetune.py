@@ -445,7 +445,7 @@ def _check_supported(model, criterion):
         tr = is_trainable_param(key_to_param(n)[0])
         if tr != bool(p.requires_grad):
             raise NotImplementedError("%s.requires_grad=%s: the fused step trains exactly the reference's freeze rule "
-                                      "(adapters, gates, head -- main_image.py:250-256); --fulltune / partial freezing is "
+                                      "(adapters, gates, head, fc_norm where the model has it -- main_image.py:250-256); --fulltune / partial freezing is "
                                       "not supported" % (n, p.requires_grad))
 
 

@@ -192,12 +192,22 @@ class VisionTransformer(nn.Module):
                  precision=None, max_batch=None, train_mode=None, inference_only=None, wide_head=None):
         super().__init__()
         fixed = dict(img_size=(img_size, 224), patch_size=(patch_size, 16), in_chans=(in_chans, 3), embed_dim=(embed_dim, 768),
-                     num_heads=(num_heads, 12), mlp_ratio=(mlp_ratio, 4.0), qkv_bias=(qkv_bias, True), global_pool=(global_pool, 'token'),
+                     num_heads=(num_heads, 12), mlp_ratio=(mlp_ratio, 4.0), qkv_bias=(qkv_bias, True),
                      class_token=(class_token, True), qk_norm=(qk_norm, False), init_values=(init_values, None),
                      no_embed_class=(no_embed_class, False), pre_norm=(pre_norm, False))
         for k, (got, want) in fixed.items():
             if got != want:
                 raise NotImplementedError("%s=%r: the HIP path implements vit_base_patch16_224_in21k (%s=%r)" % (k, got, k, want))
+        # global_pool / fc_norm (reference :259-261,314-317,375-380): 'token' (cls row) and 'avg' (mean of the patch rows); with fc_norm --
+        # the reference's default for 'avg' -- the final norm is an identity and the head's LayerNorm is the trainable fc_norm (absent from
+        # the IN21K checkpoint).  '' (no pooling) and ('avg', fc_norm=False) -- LayerNorm over all 197 rows before the mean, a frozen norm;
+        # no protocol uses it -- have no HIP path.
+        if global_pool not in ('avg', 'token'):
+            raise NotImplementedError("global_pool=%r: the HIP path implements vit_base_patch16_224_in21k (global_pool='token' or 'avg')" % (global_pool,))
+        use_fc_norm = global_pool == 'avg' if fc_norm is None else bool(fc_norm)
+        if global_pool == 'avg' and not use_fc_norm:
+            raise NotImplementedError("global_pool='avg' with fc_norm=False: the HIP path implements 'avg' with fc_norm (the reference's default, "
+                                      "the MAE / AdaptFormer protocol) and 'token' with or without it")
         if max(drop_rate, pos_drop_rate, patch_drop_rate, proj_drop_rate, attn_drop_rate) > 0:
             raise NotImplementedError("dropout rates other than the adapter's are 0 in every reference entry point")
         if not 0.0 <= float(drop_path_rate) < 1.0:
@@ -222,7 +232,9 @@ class VisionTransformer(nn.Module):
         self.blocks = nn.Sequential(*[
             block_fn(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, tuning_config=tuning_config,
                      layer_id=i, select=select_config.open and i >= select_config.keep_layers) for i in range(depth)])
-        self.norm = _LayerNormParams(embed_dim)
+        self.use_fc_norm = use_fc_norm
+        self.norm = _LayerNormParams(embed_dim) if not use_fc_norm else nn.Identity()   # reference :314
+        self.fc_norm = _LayerNormParams(embed_dim) if use_fc_norm else nn.Identity()    # reference :316 (ones / zeros at init)
         self.head = _LinearParams(embed_dim, num_classes)
         nn.init.normal_(self.cls_token, std=1e-6)
         self.apply(self.init_weights)
@@ -289,7 +301,7 @@ class VisionTransformer(nn.Module):
                             adapter_dropout=self.blocks[0].adaptmlp.dropout, tau=self.blocks[0].mlp_token_select.tau,
                             threshold=self.blocks[0].mlp_token_select.threshold, frames=self._frames or 1,
                             adapter_ln=self.blocks[0].adaptmlp.adapter_ln_code, inference=self.inference_only,
-                            wide_head=self.wide_head)
+                            wide_head=self.wide_head, avg_pool=self.global_pool == 'avg', fc_norm=self.use_fc_norm)
             self._engine = eng
             self._sync_state = None
         if not self.inference_only and getattr(eng, "drop_path_rate", 0.0) != self.drop_path_rate:   # (stochastic depth: training passes only)
@@ -370,7 +382,8 @@ class VisionTransformer(nn.Module):
 
     @torch.no_grad()
     def forward_features(self, x, complete_model=False, gumbel=None, keep_mask=None):
-        """Reference :343-371: the block stack's output after the final norm, ``(tokens [B,197,768], {"token_select", "token_logits"})``.
+        """Reference :343-371: the block stack's output after the final norm, ``(tokens [B,197,768], {"token_select", "token_logits"})``
+        (with fc_norm the final norm is an identity, :314: the un-normalised tokens).
         Runs the same HIP forward with DYT_F_TOKENS_OUT (every token of the last block is then computed: no cls-only tail) and the final
         LayerNorm through the C ABI's ``dyt_layernorm``.  Forward only -- training goes through ``forward`` / the fused step."""
         import ctypes
@@ -391,6 +404,8 @@ class VisionTransformer(nn.Module):
         seed = (torch.initial_seed() * 1000003 + self._seed_counter) & (2 ** 63 - 1)
         tok, ts, tl = eng.forward_features_tokens(x, training=self.training, complete_model=bool(complete_model),
                                                   masked_dense=(self.training and self.train_mode == "masked"), g1=g1, g2=g2, keep_mask=keep_mask, seed=seed)
+        if self.use_fc_norm:
+            return tok, dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))
         out = torch.empty_like(tok)
         check(lib().dyt_layernorm(ptr(tok.view(-1, self.embed_dim)), ptr(self.norm.weight.detach().float().contiguous()),
                                   ptr(self.norm.bias.detach().float().contiguous()), ptr(out.view(-1, self.embed_dim)),
@@ -399,13 +414,21 @@ class VisionTransformer(nn.Module):
 
     @torch.no_grad()
     def forward_head(self, x, pre_logits: bool = False):
-        """Reference :375-380: cls pooling (``global_pool='token'``; fc_norm / head_drop are identities) and the head, on the output of
-        ``forward_features``.  The head GEMM runs through ``dyt_linear`` in exact fp32 (class count padded to the kernel's 128-column
+        """Reference :375-380: pooling (``global_pool='token'``: the cls row, ``'avg'``: the mean of the patch rows), ``fc_norm`` (an
+        identity unless the model was built with it; else through ``dyt_layernorm``) and the head, on the output of ``forward_features``.  The head GEMM runs through ``dyt_linear`` in exact fp32 (class count padded to the kernel's 128-column
         tile on the host).  Forward only."""
         from _lib import check, lib, ptr, stream_ptr
         if not x.is_cuda:
             raise DyTError("forward_head runs on a HIP device only")
-        cls = x[:, 0].float().contiguous()
+        if self.global_pool == 'avg':
+            cls = x[:, self.num_prefix_tokens:].float().mean(dim=1).contiguous()   # (host-side plumbing of the sub-module API; the model's forward pools in avg_pool_fwd)
+        else:
+            cls = x[:, 0].float().contiguous()
+        if self.use_fc_norm:
+            normed = torch.empty_like(cls)
+            check(lib().dyt_layernorm(ptr(cls), ptr(self.fc_norm.weight.detach().float().contiguous()),
+                                      ptr(self.fc_norm.bias.detach().float().contiguous()), ptr(normed), cls.shape[0], stream_ptr()))
+            cls = normed
         if pre_logits:
             return cls
         C = self.num_classes

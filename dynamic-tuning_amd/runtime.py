@@ -2,14 +2,14 @@
 
 Thin plumbing above the C ABI (include/dyt_hip.h): it owns the flat trainable buffer the
 library reads (so that ONE AdamW launch and ONE all-reduce cover the 74 trainable tensors of
-main_image.py:250-256) and forwards every call to the shared library on torch's current
+main_image.py:250-256; 76 with fc_norm) and forwards every call to the shared library on torch's current
 stream.  No arithmetic happens here.
 """
 import ctypes
 
 import torch
 
-from _lib import (CREATE_WIDE_HEAD, Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
+from _lib import (CREATE_AVG_POOL, CREATE_FC_NORM, CREATE_WIDE_HEAD, Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
                   F_TRAINING, OPT_F32_SPLIT16, OPT_LEARNABLE_SCALE, PREC_BF16, PREC_FP16, PREC_FP16X3, PREC_FP16F8, PREC_FP16X3F, PREC_FP16X3H, PREC_FP16X3Q, PREC_FP32,
                   check, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
 
@@ -41,7 +41,8 @@ def parse_precision(p):
 
 class DyTEngine:
     def __init__(self, num_classes, ffn_num, adapter_scale, device, precision=PREC_BF16, max_batch=128, depth=12,
-                 slots=2, adapter_dropout=0.1, tau=5.0, threshold=0.5, frames=1, adapter_ln=0, inference=False, wide_head=False):
+                 slots=2, adapter_dropout=0.1, tau=5.0, threshold=0.5, frames=1, adapter_ln=0, inference=False, wide_head=False,
+                 avg_pool=False, fc_norm=False):
         if torch.device(device).type != "cuda":
             raise DyTError("the DyT path runs on a HIP device only (got %s); there is no CPU path" % (device,))
         self.device = torch.device(device)
@@ -69,10 +70,16 @@ class DyTEngine:
         # wide_head=True (DYT_CREATE_WIDE_HEAD): the head on the exact-fp32 MFMA kernels, num_classes up to 65 536; False: the row-kernel
         # head (up to 1024 classes), bit for bit what every measured configuration runs
         self.wide_head = bool(wide_head)
+        # avg_pool=True (DYT_CREATE_AVG_POOL, the reference's global_pool='avg'): the head reads the mean of the patch tokens; fc_norm=True
+        # (DYT_CREATE_FC_NORM; implied by avg_pool): its LayerNorm is the trainable fc_norm.{weight,bias} of the flat buffer
+        self.avg_pool = bool(avg_pool)
+        self.fc_norm = bool(fc_norm) or self.avg_pool
+        create_flags = ((CREATE_WIDE_HEAD if self.wide_head else 0) | (CREATE_AVG_POOL if self.avg_pool else 0) |
+                        (CREATE_FC_NORM if self.fc_norm else 0))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            if self.wide_head:
-                self._ck(self.L.dyt_ctx_create_ex(ctypes.byref(self.cfg), CREATE_WIDE_HEAD, ctypes.byref(h)))
+            if create_flags:
+                self._ck(self.L.dyt_ctx_create_ex(ctypes.byref(self.cfg), create_flags, ctypes.byref(h)))
             else:
                 self._ck(self.L.dyt_ctx_create(ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h

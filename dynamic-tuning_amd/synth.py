@@ -36,8 +36,10 @@ POOL_SHAPES = {  # video model only (video_models/video_vision_transformer_IN21K
 }
 
 
-def param_shapes(num_classes=100, ffn_num=64, depth=DEPTH, video=False):
-    """Ordered ``name -> shape`` for the reference model's ``state_dict()`` (video=True: the video model's)."""
+def param_shapes(num_classes=100, ffn_num=64, depth=DEPTH, video=False, head_norm="norm"):
+    """Ordered ``name -> shape`` for the reference model's ``state_dict()`` (video=True: the video model's; head_norm="fc_norm": the model
+    built with fc_norm -- global_pool='avg' or fc_norm=True -- whose final norm is an identity)."""
+    assert head_norm in ("norm", "fc_norm")
     shapes = {
         "cls_token": (1, 1, DIM),
         "pos_embed": (1, NUM_TOKENS, DIM),
@@ -64,8 +66,8 @@ def param_shapes(num_classes=100, ffn_num=64, depth=DEPTH, video=False):
         shapes[p + "adaptmlp.up_proj.bias"] = (DIM,)
         shapes[p + "mlp_token_select.mlp_head.weight"] = (1, DIM)
         shapes[p + "mlp_token_select.mlp_head.bias"] = (1,)
-    shapes["norm.weight"] = (DIM,)
-    shapes["norm.bias"] = (DIM,)
+    shapes[head_norm + ".weight"] = (DIM,)
+    shapes[head_norm + ".bias"] = (DIM,)
     shapes["head.weight"] = (num_classes, DIM)
     shapes["head.bias"] = (num_classes,)
     if video:
@@ -74,8 +76,8 @@ def param_shapes(num_classes=100, ffn_num=64, depth=DEPTH, video=False):
 
 
 def is_trainable(name):
-    """Freeze rule of ``main_image.py:250-256``: adapters, gates and the head train."""
-    return (("adaptmlp." in name) or ("mlp_token_select." in name) or name.startswith("head.") or
+    """Freeze rule of ``main_image.py:250-256``: adapters, gates and the head train -- and ``fc_norm.*``, which the checkpoint lacks."""
+    return (("adaptmlp." in name) or ("mlp_token_select." in name) or name.startswith("head.") or name.startswith("fc_norm.") or
             name == "query_token" or name.startswith("attentive_blocks."))   # video: missing from the ViT checkpoint
 
 
@@ -89,8 +91,11 @@ def _normal(name, shape, seed, std, mean=0.0):
 
 
 def make_state_dict(num_classes=100, ffn_num=64, seed=0, kind="test", depth=DEPTH,
-                    gate_bias=0.0, video=False):
+                    gate_bias=0.0, video=False, head_norm="norm"):
     """Synthetic weights.
+
+    head_norm="fc_norm": the head's LayerNorm tensors are named ``fc_norm.*`` (there is no ``norm.*``); kind="test" gives them the same
+        non-trivial values, so that the gradients of gamma / beta are exercised.
 
     kind="bench": what the reference's own init gives (trunc-normal(0.02) linears with
         zero biases, LN weight 1 / bias 0, ``pos_embed ~ 0.02 N``, ``cls ~ 1e-6 N``;
@@ -103,14 +108,14 @@ def make_state_dict(num_classes=100, ffn_num=64, seed=0, kind="test", depth=DEPT
     """
     sd = {}
     test = kind == "test"
-    for name, shape in param_shapes(num_classes, ffn_num, depth, video).items():
+    for name, shape in param_shapes(num_classes, ffn_num, depth, video, head_norm).items():
         if name == "cls_token":
             t = _normal(name, shape, seed, 0.02 if test else 1e-6)
         elif name == "pos_embed":
             t = _normal(name, shape, seed, 0.02)
         elif name == "query_token":   # reference init is zeros (:407): LN of a constant row would be degenerate
             t = _normal(name, shape, seed, 0.02 if not test else 0.5)
-        elif ".norm" in name or name.startswith("norm."):
+        elif ".norm" in name or name.startswith("norm.") or name.startswith("fc_norm."):
             if name.endswith("weight"):
                 t = _normal(name, shape, seed, 0.1, 1.0) if test else torch.ones(shape)
             else:

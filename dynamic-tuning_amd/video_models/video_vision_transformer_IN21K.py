@@ -53,6 +53,9 @@ class VisionTransformer(_ImageViT):
     def __init__(self, *args, inference_only=None, **kwargs):
         if "wide_head" in kwargs:
             raise TypeError("the video model has no wide_head keyword: its pooling head is not part of the wide-head form")
+        if kwargs.get("global_pool", "token") != "token" or kwargs.get("fc_norm") not in (None, False):
+            raise NotImplementedError("global_pool=%r, fc_norm=%r: the video model pools with its attentive head (global_pool='token', no fc_norm)"
+                                      % (kwargs.get("global_pool", "token"), kwargs.get("fc_norm")))
         super().__init__(*args, inference_only=inference_only, wide_head=False, **kwargs)   # (> 1024 classes: the library's refusal)
         self.query_token = nn.Parameter(torch.zeros(1, 1, self.embed_dim))          # :407
         self.attentive_blocks = AttentiveBlock(self.embed_dim, 12, qkv_bias=True)   # :408-410

@@ -98,6 +98,7 @@ enum dyt_param {
     DYT_P_POOL_PROJ_W, DYT_P_POOL_PROJ_B,             /* T attentive_blocks.cross_attn.proj [768,768] */
     DYT_P_AD_SCALE,     /* T blocks.i.adaptmlp.scale [1] -- only with tuning_config.ffn_adapter_scalar == "learnable_scalar" (DYT_OPT_LEARNABLE_SCALE) */
     DYT_P_AD_LN_W, DYT_P_AD_LN_B,   /* T blocks.i.adaptmlp.adapter_layer_norm_before.{weight,bias} [768] -- only with dyt_config::adapter_ln != 0 */
+    DYT_P_FC_NORM_W, DYT_P_FC_NORM_B,   /* T fc_norm.{weight,bias} [768] -- only with DYT_CREATE_FC_NORM / DYT_CREATE_AVG_POOL (ABI v5) */
     DYT_P_COUNT
 };
 
@@ -157,6 +158,32 @@ int dyt_ctx_create(const dyt_config* cfg, dyt_ctx** out);
  *                         valid together with dyt_config::inference_only.  Adds [ceil(C/1024)][max_batch][768] floats per slot to
  *                         the training layout. */
 #define DYT_CREATE_WIDE_HEAD 1u
+/* The reference's global_pool / fc_norm constructor arguments (models/vision_transformer_IN21K.py:205,216,259-261,314-317; forward_head
+ * :375-380).  ABI v5.  With neither bit set every offset, launch and result bit is what it was.
+ *   DYT_CREATE_FC_NORM    the head's LayerNorm (eps 1e-6, the arithmetic of the final norm on the cls rows) is the reference's `fc_norm`
+ *                         (:316, applied at :378) and the final `norm` is an identity (:314).  Its weight and bias are TRAINABLE -- the
+ *                         ViT-B/16 IN21K checkpoint has no fc_norm.*, so the freeze rule of main_image.py:250-256 leaves them on -- and
+ *                         live in the caller's flat buffer as DYT_P_FC_NORM_W / DYT_P_FC_NORM_B: two [768] tensors directly behind
+ *                         head.bias, inside part 0 of dyt_grad_part (final when the head's backward is, before any block's).
+ *                         dyt_trainable_offset serves the two ids in such a context only; dyt_set_frozen(DYT_P_NORM_W / _B) returns
+ *                         DYT_ERR_ARG there (the text names the flag).  The head backward additionally leaves dy = dlogits W_head
+ *                         ([max_batch][768] per slot, training layout, counted by dyt_ctx_bytes) and one kernel adds
+ *                         d_gamma[c] += sum_b dy[b][c] xhat[b][c], d_beta[c] += sum_b dy[b][c] in ascending image order, xhat recomputed
+ *                         from the saved (mean, rstd) and the LayerNorm's input row.
+ *   DYT_CREATE_AVG_POOL   global_pool='avg' (:377): the row fed to that LayerNorm is the mean of the 196 patch-token rows of the last
+ *                         block's output, cls row excluded, instead of the cls row.  Goes with DYT_CREATE_FC_NORM (the reference's default
+ *                         for 'avg', :261) and switches the cls-only tail off (DYT_OPT_CLS_TAIL stays 0: every patch token of the last
+ *                         block reaches the head).  Per output channel the 196 rows are summed as 7 runs of 28 consecutive rows, each run
+ *                         a chain in ascending token order, the run sums added in ascending order, the result divided by 196.  The
+ *                         backward writes the whole gradient stream once: cls rows exactly 0, every patch row dpooled / 196.
+ *                         Adds [max_batch][768] floats per slot.  The bit is given TOGETHER with DYT_CREATE_FC_NORM (6u): on its own it
+ *                         would be the reference's ('avg', fc_norm=False) -- LayerNorm over all 197 rows in front of the mean, with the
+ *                         frozen norm -- which has no HIP path and returns DYT_ERR_ARG (the text names create_flags and both bits).
+ *                         runtime.DyTEngine(avg_pool=True) and the models' global_pool='avg' set both.
+ * Both are image-model flags (frames > 1: DYT_ERR_ARG) and combine with DYT_CREATE_WIDE_HEAD, dyt_config::inference_only,
+ * dyt_config::adapter_ln and every precision mode; the head stays fp32, without atomics, bit-reproducible. */
+#define DYT_CREATE_AVG_POOL 2u
+#define DYT_CREATE_FC_NORM 4u
 int dyt_ctx_create_ex(const dyt_config* cfg, uint32_t create_flags, dyt_ctx** out);
 int dyt_ctx_destroy(dyt_ctx* ctx);
 /* bytes of device memory the context holds (weights + workspace) */
@@ -413,6 +440,16 @@ int dyt_adapter_bwd(const float* x, const float* down_w, const float* down_b, co
  * dlogits NULL: forward only, no gradient is touched.  C = 1 ... 65 536. */
 int dyt_head_wide(const float* cls_x, const float* norm_w, const float* norm_b, const float* head_w, const float* head_b,
                   float* logits, const float* dlogits, float* dx, float* d_head_w, float* d_head_b, int batch, int C, void* stream);
+/* The pooled head (DYT_CREATE_AVG_POOL / DYT_CREATE_FC_NORM, optionally DYT_CREATE_WIDE_HEAD in create_flags) without a context, exactly
+ * the launches the context path runs (reference forward_head, models/vision_transformer_IN21K.py:375-380): logits [B,C] =
+ * fc_norm(row_b) head_w^T + head_b, row_b = mean of the 196 patch rows of x_tokens [B,197,768] (AVG_POOL | FC_NORM) or its cls row (FC_NORM alone).
+ * With dlogits [B,C] also the backward: dx_tokens [B,197,768] is OVERWRITTEN with the gradient w.r.t. x_tokens (AVG_POOL: cls rows 0,
+ * patch rows dpooled / 196; FC_NORM alone: the cls rows, zero elsewhere); d_fc_norm_w / d_fc_norm_b [768], d_head_w [C,768], d_head_b [C]
+ * are ACCUMULATED (+=) and may each be NULL.  dlogits NULL: forward only.  C = 1 ... 1024, with DYT_CREATE_WIDE_HEAD 1 ... 65 536.
+ * Unit-test entry: allocates its scratch and synchronises. */
+int dyt_pool_head(const float* x_tokens, const float* fc_norm_w, const float* fc_norm_b, const float* head_w, const float* head_b,
+                  float* logits, const float* dlogits, float* dx_tokens, float* d_fc_norm_w, float* d_fc_norm_b,
+                  float* d_head_w, float* d_head_b, int batch, int C, uint32_t create_flags, void* stream);
 /* the token-gathered MLP of block `layer` (frozen weights of the context; models/model_speed_test.py:297-305): for the tokens with a
  * non-zero mask, x[t] += fc2(gelu(fc1(LN2(u[t])))); u, x fp32 [batch*197,768] (x in place), mask [batch*197]; total_out[1] (device,
  * may be NULL) = number of gathered tokens */
