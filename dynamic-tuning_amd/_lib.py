@@ -99,6 +99,22 @@ class DyTError(RuntimeError):
     pass
 
 
+ADAMW_MAX_SEGMENTS = 128   # DYT_ADAMW_MAX_SEGMENTS
+
+
+class AdamwSegment(ctypes.Structure):
+    """dyt_adamw_segment: elements [previous end, end) of the flat buffer take this lr / weight_decay (dyt_adamw_segments)."""
+    _fields_ = [("end", ctypes.c_int64), ("lr", ctypes.c_float), ("weight_decay", ctypes.c_float)]
+
+
+def adamw_segment_array(table):
+    """[(end, lr, weight_decay), ...] -> the host array dyt_adamw_segments reads during the call (and never afterwards)."""
+    arr = (AdamwSegment * len(table))()
+    for k, (end, lr, wd) in enumerate(table):
+        arr[k].end, arr[k].lr, arr[k].weight_decay = int(end), float(lr), float(wd)
+    return arr
+
+
 def inference_only_default(explicit=None, tuning_config=None):
     """The models' ``inference_only`` keyword: the explicit value, else ``tuning_config.dyt_inference_only``, else the environment's
     DYT_INFERENCE_ONLY, else False."""
@@ -156,6 +172,7 @@ SYMBOLS = {
     "dyt_loss": (_i, [_vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "dyt_adamw": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _f, _f, _f, _f, _f, _vp]),
     "dyt_adamw_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _vp]),
+    "dyt_adamw_segments": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp]),
     "dyt_step_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _u64, _f, _f, _f, _f, _vp, _vp, _vp, _vp,
                               _vp, _vp]),
     "dyt_seed": (_i, [_vp, _u64, _vp]),
@@ -190,6 +207,9 @@ SYMBOLS = {
                               ctypes.POINTER(ctypes.c_double)]),
 }
 
+# Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
+# build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
+OPTIONAL_SYMBOLS = {"dyt_adamw_segments"}
 
 _lib16 = None
 
@@ -204,6 +224,8 @@ def lib(fp16=False):
                 raise DyTError("%s not found: build it with `make -C dynamic-tuning_amd/csrc`" % LIB_PATH_F16)
             L = ctypes.CDLL(LIB_PATH_F16)
             for name, (res, args) in SYMBOLS.items():
+                if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
+                    continue
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -228,6 +250,8 @@ def lib(fp16=False):
             ctypes.CDLL(rccl, mode=ctypes.RTLD_GLOBAL)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
+            if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

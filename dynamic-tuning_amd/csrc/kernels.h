@@ -265,6 +265,14 @@ int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float 
 int launch_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, int* state, float lr, float b1, float b2,
                          float eps, float wd, float gscale, hipStream_t s);
 
+// ... with per-segment lr / weight_decay (parameter groups): segment k covers elements [s[k-1].end, s[k].end) of the flat buffer, the last
+// end is n.  The table is passed to the kernel by value: the launch captures it.  state: as above, or null for the unguarded form with
+// the caller's bias corrections.  (The layout of dyt_adamw_segment, include/dyt_hip.h; step.hip asserts it.)
+struct AdamwSeg { int64_t end; float lr; float wd; };
+struct AdamwSegTable { AdamwSeg s[128]; };
+int launch_adamw_segments(float* p, const float* g, float* m, float* v, int64_t n, int* state, const AdamwSegTable& table, int nseg,
+                          float b1, float b2, float eps, float bc1, float rsqrt_bc2, float gscale, hipStream_t s);
+
 // backward prep for one block: g_at = AT(g) ; dH[dst_of[t]] = AT(g[t] * mask) ;
 // dmask[token] = <g[token], h[r]> for kept rows (0 elsewhere)
 struct BwdPrepArgs {

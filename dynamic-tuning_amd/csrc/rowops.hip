@@ -842,11 +842,12 @@ int launch_loss(const LossArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 // AdamW over the flat trainable buffer
 // ------------------------------------------------------------------------------------------
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                             float bc1, float rsqrt_bc2, float gscale) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+// The per-element update: ONE expression for adamw_kernel, adamw_guarded_kernel and adamw_segments_kernel, so that the compiler contracts
+// it (fma) the same way in all three and their results agree bit for bit.  bc1 / rsqrt_bc2: the bias corrections, formed in double and
+// rounded to float once by the caller.
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
+                                             float bc1, float rsqrt_bc2, float gscale) {
     const float gi = g[i] * gscale;
     float pi = p[i] * (1.0f - lr * wd);
     const float mi = b1 * m[i] + (1.0f - b1) * gi;
@@ -854,6 +855,13 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
     pi -= (lr / bc1) * (mi / denom);
     p[i] = pi; m[i] = mi; v[i] = vi;
+}
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                             float bc1, float rsqrt_bc2, float gscale) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
 }
 // ---- overflow-guarded update (the reference's GradScaler.step / update, misc.py:256-272: an update whose gradient holds inf / NaN is
 // ---- skipped and counted; everything stays on the device: state = {updates applied, updates skipped, non-finite flag of this call, -}
@@ -879,14 +887,47 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ 
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || state[2] != 0) return;   // non-finite gradient somewhere: parameters and moments stay as they are
-    const float bc1 = bc_s[0], rsqrt_bc2 = bc_s[1];
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
+    adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc_s[0], bc_s[1], gscale);
+}
+// ---- parameter groups: the same update with lr and weight_decay taken per SEGMENT of the flat buffer (torch.optim.AdamW with several
+// ---- param_groups; util/lr_decay.py makes ~26).  The table travels by value in the kernel arguments, so it is captured at launch and the
+// ---- caller may rewrite its own copy at once.  Lookup without any per-thread indexing of the argument (that would be copied to scratch):
+// ---- a workgroup owns elements [base, base + 256); it binary-searches the first segment that ends past `base` with a workgroup-uniform
+// ---- index (scalar loads), then walks the segments that begin inside its range, again uniformly, and every thread keeps the
+// ---- hyper-parameters of the last segment that begins at or before its element.  state == null: bc1 / rsqrt_bc2 come from the host
+// ---- (adamw_kernel's form); else adamw_guarded_kernel's form.  (The search's ~log2(segments) dependent scalar loads stand in front of the
+// ---- element's loads: +9 % kernel time at 26 segments over 18 M elements, none with one segment -- DESIGN.md 7k, also on why the loads
+// ---- are not hoisted above it.)
+__global__ __launch_bounds__(256) void adamw_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                      float* __restrict__ v, int64_t n, const AdamwSegTable T, int nseg, float b1, float b2, float eps,
+                                      float bc1_host, float rsqrt_bc2_host, float gscale, const int* __restrict__ state) {
+    __shared__ float bc_s[2];
+    if (threadIdx.x == 0) {
+        if (state) {   // bias corrections in double, rounded to fp32 once: adamw_guarded_kernel's lines
+            const double step = (double)(state[0] + 1);
+            bc_s[0] = (float)(1.0 - pow((double)b1, step));
+            bc_s[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+        } else {
+            bc_s[0] = bc1_host;
+            bc_s[1] = rsqrt_bc2_host;
+        }
+    }
+    const int64_t base = (int64_t)blockIdx.x * 256;
+    int lo = 0, hi = nseg - 1;   // the last segment ends at n > base: the answer exists
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (T.s[mid].end > base) hi = mid; else lo = mid + 1;
+    }
+    const int64_t i = base + threadIdx.x;
+    float lr = T.s[lo].lr, wd = T.s[lo].wd;
+    for (int s = lo + 1; s < nseg; ++s) {
+        const int64_t begin = T.s[s - 1].end;
+        if (begin >= base + 256) break;
+        if (i >= begin) { lr = T.s[s].lr; wd = T.s[s].wd; }
+    }
+    __syncthreads();
+    if (i >= n || (state && state[2] != 0)) return;   // non-finite gradient somewhere: every segment stays as it is
+    adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc_s[0], bc_s[1], gscale);
 }
 __global__ void adamw_count_kernel(int* __restrict__ state) {
     if (threadIdx.x == 0) { if (state[2]) state[1] += 1; else state[0] += 1; }
@@ -897,6 +938,19 @@ int launch_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n
     hipLaunchKernelGGL(grad_nonfinite_kernel, dim3((unsigned)std::min<int64_t>(256, (n + 255) / 256)), dim3(256), 0, s, g, n, state);
     hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, gscale, state);
     hipLaunchKernelGGL(adamw_count_kernel, dim3(1), dim3(64), 0, s, state);
+    LAUNCH_CHECK();
+    return 0;
+}
+int launch_adamw_segments(float* p, const float* g, float* m, float* v, int64_t n, int* state, const AdamwSegTable& table, int nseg,
+                          float b1, float b2, float eps, float bc1, float rsqrt_bc2, float gscale, hipStream_t s) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (state) {
+        if (hipMemsetAsync(state + 2, 0, sizeof(int), s) != hipSuccess) { set_error("hipMemsetAsync failed"); return -2; }
+        hipLaunchKernelGGL(grad_nonfinite_kernel, dim3((unsigned)std::min<int64_t>(256, (n + 255) / 256)), dim3(256), 0, s, g, n, state);
+    }
+    hipLaunchKernelGGL(adamw_segments_kernel, grid, dim3(256), 0, s, p, g, m, v, n, table, nseg, b1, b2, eps, bc1, rsqrt_bc2, gscale,
+                       (const int*)state);
+    if (state) hipLaunchKernelGGL(adamw_count_kernel, dim3(1), dim3(64), 0, s, state);
     LAUNCH_CHECK();
     return 0;
 }

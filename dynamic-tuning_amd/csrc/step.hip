@@ -50,6 +50,43 @@ extern "C" int dyt_adamw_guarded(float* param, const float* grad, float* exp_avg
                                 static_cast<hipStream_t>(stream));
 }
 
+// The same update with lr and weight_decay per segment of the flat buffer (torch.optim.AdamW with several param_groups).  `segments` is a
+// host array, read here and never again: it is copied into the kernel's arguments.  state != NULL: dyt_adamw_guarded's semantics over the
+// WHOLE buffer (`step` ignored); state == NULL: dyt_adamw's with the 1-based `step`.
+static_assert(sizeof(dyt_adamw_segment) == sizeof(AdamwSeg) && offsetof(dyt_adamw_segment, lr) == offsetof(AdamwSeg, lr) &&
+              offsetof(dyt_adamw_segment, weight_decay) == offsetof(AdamwSeg, wd) && DYT_ADAMW_MAX_SEGMENTS == 128, "segment table layout");
+extern "C" int dyt_adamw_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, int32_t* state, int step,
+                                  const dyt_adamw_segment* segments, int num_segments, float beta1, float beta2, float eps,
+                                  float grad_scale, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !segments || numel < 1 || (!state && step < 1)) { set_error("bad argument"); return DYT_ERR_ARG; }
+    if (num_segments < 1 || num_segments > DYT_ADAMW_MAX_SEGMENTS) {
+        set_error("dyt_adamw_segments: %d segments (1 ... %d)", num_segments, DYT_ADAMW_MAX_SEGMENTS);
+        return DYT_ERR_ARG;
+    }
+    AdamwSegTable table;
+    memset(&table, 0, sizeof(table));
+    int64_t prev = 0;
+    for (int k = 0; k < num_segments; ++k) {
+        if (segments[k].end <= prev) {
+            set_error("dyt_adamw_segments: segment %d ends at %lld, not past %lld (ends must increase strictly)", k, (long long)segments[k].end, (long long)prev);
+            return DYT_ERR_ARG;
+        }
+        prev = segments[k].end;
+        table.s[k].end = segments[k].end; table.s[k].lr = segments[k].lr; table.s[k].wd = segments[k].weight_decay;
+    }
+    if (prev != numel) {
+        set_error("dyt_adamw_segments: the last segment ends at %lld, the buffer has %lld elements", (long long)prev, (long long)numel);
+        return DYT_ERR_ARG;
+    }
+    float bc1 = 1.0f, rsqrt_bc2 = 1.0f;
+    if (!state) {   // dyt_adamw's lines
+        bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+        rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+    }
+    return launch_adamw_segments(param, grad, exp_avg, exp_avg_sq, numel, state, table, num_segments, beta1, beta2, eps, bc1, rsqrt_bc2,
+                                 grad_scale, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* targets, int batch, int flags,
                                 const float* trainable, const float* g1, const float* g2, const uint8_t* keep_mask,
                                 uint64_t seed, float token_target_ratio, float token_loss_ratio, float token_minimal,

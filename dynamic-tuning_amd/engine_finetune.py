@@ -46,6 +46,91 @@ def gradscaler_dict(scale_log2, growth_tracker, skipped, growth_interval):
                 scale_log2=None if scale_log2 is None else int(scale_log2), skipped=int(skipped))
 
 
+SHARED_HYPER = ("betas", "eps", "amsgrad", "maximize")   # one value for the whole flat buffer; lr and weight_decay are per group
+
+
+def shared_hyper(groups):
+    """(beta1, beta2, eps) of a list of param-group dicts.  The update kernel takes lr and weight_decay per segment and everything else
+    once: groups that differ in ``betas`` / ``eps``, or any group with ``amsgrad`` / ``maximize``, are refused by the key's name."""
+    first = groups[0]
+    for key in ("amsgrad", "maximize"):
+        if any(g.get(key) for g in groups):
+            raise NotImplementedError("%s is not implemented by the fused AdamW kernel" % key)
+    for k, g in enumerate(groups[1:], 1):
+        for key in ("betas", "eps"):
+            a, b = first.get(key), g.get(key)
+            if (tuple(a) if key == "betas" else a) != (tuple(b) if key == "betas" else b):
+                raise NotImplementedError("param group %d has %s=%r, group 0 has %r: the fused AdamW kernel takes one %s for all groups "
+                                          "(lr and weight_decay may differ)" % (k, key, b, a, key))
+    b1, b2 = first["betas"]
+    return float(b1), float(b2), float(first["eps"])
+
+
+def group_positions(group_params, tensors):
+    """Per group, the positions of its ``params`` in ``tensors`` (the model's trainable tensors, named_parameters() order).  An entry is
+    a tensor (looked up by identity) or already a position.  Together the groups must hold every trainable tensor exactly once -- any
+    split, any order; anything else is refused."""
+    where = {id(t): i for i, t in enumerate(tensors)}
+    seen, out = set(), []
+    for k, params in enumerate(group_params):
+        idx = []
+        for q in params:
+            i = int(q) if isinstance(q, int) else where.get(id(q))
+            if i is None or not 0 <= i < len(tensors):
+                raise NotImplementedError("param group %d holds a tensor that is not one of the model's %d trainable tensors (adapters, gates, "
+                                          "head, fc_norm where the model has it: main_image.py:250-256,285)" % (k, len(tensors)))
+            if i in seen:
+                raise NotImplementedError("trainable tensor %d is held twice by the optimizer's param groups" % i)
+            seen.add(i)
+            idx.append(i)
+        out.append(idx)
+    if len(seen) != len(tensors):
+        missing = sorted(set(range(len(tensors))) - seen)
+        raise NotImplementedError("the optimizer's param groups hold %d tensors, the model trains %d (first missing: position %d): the fused "
+                                  "step updates exactly the reference's trainable tensors" % (len(seen), len(tensors), missing[0]))
+    return out
+
+
+def segment_layout(slices, group_params, total=None):
+    """[(end, group)] over the flat buffer in offset order.  ``slices[i]`` = (offset, numel) of trainable tensor i (dyt_trainable_offset);
+    ``group_params[k]`` = the positions group k holds; ``total`` = the buffer's length (default: the end of the last tensor).  The
+    library aligns every tensor's offset, so a tensor may be followed by a few padding elements (zero in the parameters, the gradient
+    and both moments, and left at zero by any lr / weight_decay): they go with the tensor in front of them.  Depends on the membership
+    alone, so it is computed once per engine."""
+    pos = group_positions(group_params, list(range(len(slices))))
+    rows = sorted((slices[i][0], slices[i][1], k) for k, idx in enumerate(pos) for i in idx)
+    if not rows or rows[0][0] != 0:
+        raise DyTError("the first trainable tensor does not start the flat buffer")
+    layout = []
+    for j, (off, num, k) in enumerate(rows):
+        end = rows[j + 1][0] if j + 1 < len(rows) else (off + num if total is None else int(total))
+        if num < 1 or end < off + num:
+            raise DyTError("trainable tensors overlap in the flat buffer: one covers [%d, %d), the next begins at %d" % (off, off + num, end))
+        layout.append((end, k))
+    return layout
+
+
+def merge_segments(layout, groups, limit=128):
+    """[(end, lr, weight_decay)] for dyt_adamw_segments from the groups' CURRENT lr / weight_decay: neighbours in the flat buffer with equal
+    values become one segment.  ``limit`` = DYT_ADAMW_MAX_SEGMENTS."""
+    table = []
+    for end, k in layout:
+        lr, wd = float(groups[k]["lr"]), float(groups[k]["weight_decay"])
+        if table and table[-1][1] == lr and table[-1][2] == wd:
+            table[-1] = (end, lr, wd)
+        else:
+            table.append((end, lr, wd))
+    if len(table) > limit:
+        raise DyTError("%d segments of distinct (lr, weight_decay) remain after merging neighbours; dyt_adamw_segments takes %d" % (len(table), limit))
+    return table
+
+
+def adamw_segment_table(slices, groups, total=None):
+    """The segment table of one update, a pure function of the flat layout and the param groups (``params`` = positions in ``slices``)."""
+    shared_hyper(groups)
+    return merge_segments(segment_layout(slices, [g["params"] for g in groups], total), groups)
+
+
 class FusedAdamW:
     """Stands where ``torch.optim.AdamW([trainable params], lr, weight_decay)`` stands in main_image.py:285; the update
     itself is libdyt_hip's flat AdamW kernel.  Exposes ``param_groups`` so ``lr_sched.adjust_learning_rate`` works
@@ -53,13 +138,31 @@ class FusedAdamW:
     layout, allocated lazily on the engine's device), so it survives a re-created engine (larger eval batch) and can be
     restored right after construction, before any forward, as misc.load_model does.  ``state_dict()`` is in
     ``torch.optim.AdamW.state_dict()`` layout (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` in named_parameters
-    order, one param group), so the reference can resume from our checkpoints and we from its (misc.py:296-352)."""
+    order by default), so the reference can resume from our checkpoints and we from its (misc.py:296-352).
 
-    def __init__(self, model, lr=1e-3, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8):
+    Parameter groups: ``params`` may be torch's list of group dicts over the model's own parameters (what the reference's
+    util/lr_decay.param_groups_lrd returns); every group has its own ``lr`` / ``weight_decay`` (and keys such as ``lr_scale`` for
+    lr_sched), ``betas`` / ``eps`` are shared.  One group is updated by dyt_adamw(_guarded) exactly as before; several by ONE
+    dyt_adamw_segments launch over the flat buffer, with a segment table rebuilt from the groups' current values at every step."""
+
+    def __init__(self, model, params=None, lr=1e-3, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8):
         self.model = getattr(model, "module", model)
         n = len(_trainable_names(self.model))
-        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                                  foreach=None, capturable=False, differentiable=False, fused=None, params=list(range(n)))]
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None)
+        if params is None:
+            self.param_groups = [dict(defaults, params=list(range(n)))]
+        else:
+            params = list(params)
+            if not params or not all(isinstance(g, dict) for g in params):
+                raise TypeError("FusedAdamW: params is None (all trainable tensors, one group) or a list of param-group dicts")
+            self.param_groups = [dict(defaults, **g) for g in params]
+            for g in self.param_groups:
+                g["params"], g["betas"] = list(g["params"]), tuple(g["betas"])
+        self._positions = None      # per group: positions of its params among the trainable tensors (named_parameters order)
+        self._layout = None         # (engine, [(end, group)]): the flat buffer in offset order
+        self.positions()            # refuses a split that is not exactly the trainable tensors
+        shared_hyper(self.param_groups)
         self.step_count = 0
         self.exp_avg = None
         self.exp_avg_sq = None
@@ -84,6 +187,21 @@ class FusedAdamW:
 
     def zero_grad(self, set_to_none=True):
         pass  # dyt_step_fwd_bwd zeroes the flat gradient buffer itself
+
+    # ---- parameter groups ------------------------------------------------------------------------
+    def positions(self, refresh=False):
+        if self._positions is None or refresh:
+            self._positions = group_positions([g["params"] for g in self.param_groups], [p for _, p in _trainable_names(self.model)])
+            self._layout = None
+        return self._positions
+
+    def segment_table(self, eng):
+        """dyt_adamw_segments' table for the next update: the tensor -> (offset, numel) map and its offset order are cached per engine,
+        the groups' lr / weight_decay are read now."""
+        if self._layout is None or self._layout[0] is not eng:
+            slices = [eng.trainable_slice(name) for name, _ in _trainable_names(self.model)]
+            self._layout = (eng, segment_layout(slices, self.positions(), eng.n_train))
+        return merge_segments(self._layout[1], self.param_groups)
 
     # ---- state ---------------------------------------------------------------------------------
     def _state(self, eng):
@@ -127,7 +245,10 @@ class FusedAdamW:
         if max_norm is not None and max_norm > 0:
             eng.clip_grad_norm(max_norm, grad_scale)
         self.step_count += 1
-        if self.guard:   # a gradient with inf / NaN (NaN also after clipping by a NaN norm) leaves parameters and moments untouched
+        if len(self.param_groups) > 1:   # one launch over the flat buffer, lr / weight_decay per segment; the guard covers all groups
+            b1, b2, eps = shared_hyper(self.param_groups)
+            eng.adamw_segments(m, v, self.segment_table(eng), self.opt_state if self.guard else None, self.step_count, b1, b2, eps, grad_scale)
+        elif self.guard:   # a gradient with inf / NaN (NaN also after clipping by a NaN norm) leaves parameters and moments untouched
             eng.adamw_guarded(m, v, self.opt_state, g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], grad_scale)
         else:
             eng.adamw(m, v, self.step_count, g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], grad_scale)
@@ -193,6 +314,9 @@ class FusedAdamW:
         topt = self._torch
         if topt is None:
             return
+        if self.param_groups is not topt.param_groups:   # Optimizer.load_state_dict puts NEW group dicts in place: follow them
+            self.param_groups = topt.param_groups
+            self.positions(refresh=True)
         pending, step = {}, 0
         for name, p in _trainable_names(self.model):
             st = topt.state.get(p)
@@ -232,7 +356,8 @@ class FusedAdamW:
         if self.step_count > 0 or self._pending is not None:
             if eng is not None:
                 m, v = self._state(eng)
-            for i, (name, p) in enumerate(names):
+            # torch's layout: running indices in group order (for the default single group that is named_parameters order)
+            for i, (name, p) in enumerate(names[j] for idx in self.positions() for j in idx):
                 if eng is not None:
                     off, num = eng.trainable_slice(name)
                     ea, es = m[off:off + num].view(p.shape).clone(), v[off:off + num].view(p.shape).clone()
@@ -241,23 +366,29 @@ class FusedAdamW:
                 state[i] = dict(step=torch.tensor(float(self.step_count)), exp_avg=ea, exp_avg_sq=es)
         # exactly torch.optim.AdamW.state_dict()'s keys (checkpoint interchange); the gradient-scale state travels in the checkpoint's 'scaler'
         # entry like the reference's GradScaler state (misc.save_model / load_model -> scaler_state / load_scaler_state)
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(len(names)))
-        return dict(state=state, param_groups=[group])
+        groups, at = [], 0
+        for g, idx in zip(self.param_groups, self.positions()):
+            group = {k: v for k, v in g.items() if k != "params"}   # every key of the group travels (lr_scale of the layer-decay recipe too)
+            group["params"] = list(range(at, at + len(idx)))
+            at += len(idx)
+            groups.append(group)
+        return dict(state=state, param_groups=groups)
 
     def load_state_dict(self, sd):
         """Accepts torch.optim.AdamW.state_dict() of the reference (or our own): tensors may live on any device
         (misc.load_model uses map_location='cpu'); they are applied when an engine exists."""
         names = _trainable_names(self.model)
         groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(names):
-            raise ValueError("optimizer state has %d groups / %d params, the model has %d trainable tensors" % (
-                len(groups), len(groups[0]["params"]) if groups else 0, len(names)))
-        keep = {k: v for k, v in groups[0].items() if k != "params"}
-        self.param_groups[0].update(keep)
-        self.param_groups[0]["betas"] = tuple(self.param_groups[0]["betas"])
+        mine = self.positions()
+        if len(groups) != len(mine) or any(len(g["params"]) != len(idx) for g, idx in zip(groups, mine)):
+            raise ValueError("optimizer state has %d group(s) of %s params, this optimizer has %d group(s) of %s over the model's %d trainable tensors" % (
+                len(groups), [len(g["params"]) for g in groups], len(mine), [len(idx) for idx in mine], len(names)))
+        for own, g in zip(self.param_groups, groups):
+            own.update({k: v for k, v in g.items() if k != "params"})
+            own["betas"] = tuple(own["betas"])
+        shared_hyper(self.param_groups)
         pending, step = {}, 0
-        for pos, pid in enumerate(groups[0]["params"]):
+        for pos, pid in zip((j for idx in mine for j in idx), (pid for g in groups for pid in g["params"])):
             st = sd["state"].get(pid)
             if st is None:
                 continue
@@ -277,10 +408,11 @@ class FusedAdamW:
 def as_fused(optimizer, model):
     """The optimizer ``train_one_epoch`` steps with.  A ``FusedAdamW`` is taken as it is; the ``torch.optim.AdamW`` the reference's
     drivers build (main_image.py:285, main_vtab.py:269, main_video.py:316: ONE group over ``[p for p in named_parameters() if
-    p.requires_grad]``) is ADOPTED on first use: its hyper-parameter group becomes the fused optimizer's (one dict object, so
-    ``lr_sched.adjust_learning_rate`` and any later edit reach the kernel), state it may hold from ``misc.load_model`` is taken
-    over, and from then on its ``state`` aliases the fused moments -- no driver line changes.  Anything the flat AdamW kernel
-    does not implement raises."""
+    p.requires_grad]``), or one over several param groups whose tensors together are exactly those (util/lr_decay.param_groups_lrd:
+    any split, any order), is ADOPTED on first use: its ``param_groups`` list becomes the fused optimizer's (the same dict objects,
+    so ``lr_sched.adjust_learning_rate`` and any later edit of ``lr`` / ``lr_scale`` / ``weight_decay`` reach the kernel), state it
+    may hold from ``misc.load_model`` is taken over, and from then on its ``state`` aliases the fused moments -- no driver line
+    changes.  Anything the flat AdamW kernels do not implement raises."""
     m = getattr(model, "module", model)
     if getattr(m, "inference_only", False):
         raise DyTError("as_fused: the model was built with inference_only (eval forwards only); build it without inference_only to train")
@@ -292,17 +424,8 @@ def as_fused(optimizer, model):
     if not isinstance(optimizer, torch.optim.AdamW):
         raise DyTError("train_one_epoch drives the fused HIP step: pass the torch.optim.AdamW of main_image.py:285 or an "
                        "engine_finetune.FusedAdamW (got %s)" % type(optimizer).__name__)
-    if len(optimizer.param_groups) != 1:
-        raise NotImplementedError("the fused AdamW kernel updates one parameter group (got %d)" % len(optimizer.param_groups))
-    g = optimizer.param_groups[0]
-    if g.get("amsgrad") or g.get("maximize"):
-        raise NotImplementedError("amsgrad / maximize are not implemented by the fused AdamW kernel")
-    names = _trainable_names(m)
-    if len(g["params"]) != len(names) or any(a is not b for a, (_, b) in zip(g["params"], names)):
-        raise NotImplementedError("the optimizer must hold exactly the reference's trainable tensors in named_parameters() order "
-                                  "(adapters, gates, head: main_image.py:250-256,285); got %d tensors, the model trains %d"
-                                  % (len(g["params"]), len(names)))
-    fused = FusedAdamW(m, lr=g["lr"], weight_decay=g["weight_decay"], betas=g["betas"], eps=g["eps"])
+    shared_hyper(optimizer.param_groups)   # betas / eps shared by all groups, no amsgrad / maximize: refused by the key's name
+    fused = FusedAdamW(m, params=optimizer.param_groups)   # any split of exactly the trainable tensors, in any order; else refused
     fused.param_groups = optimizer.param_groups
     fused._torch = optimizer
     fused.adopt_torch_state()

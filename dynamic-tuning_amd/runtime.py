@@ -11,7 +11,7 @@ import torch
 
 from _lib import (CREATE_AVG_POOL, CREATE_FC_NORM, CREATE_WIDE_HEAD, Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
                   F_TRAINING, OPT_F32_SPLIT16, OPT_LEARNABLE_SCALE, PREC_BF16, PREC_FP16, PREC_FP16X3, PREC_FP16F8, PREC_FP16X3F, PREC_FP16X3H, PREC_FP16X3Q, PREC_FP32,
-                  check, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
+                  adamw_segment_array, check, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
 
 NP, NT, DIM = 196, 197, 768
 
@@ -328,6 +328,20 @@ class DyTEngine:
         with torch.cuda.device(self.device):
             self._ck(self.L.dyt_adamw_guarded(ptr(self.flat), ptr(self.grad), ptr(exp_avg), ptr(exp_avg_sq), self.n_train, ptr(state),
                                            lr, beta1, beta2, eps, weight_decay, grad_scale, stream_ptr()))
+
+    def adamw_segments(self, exp_avg, exp_avg_sq, table, state=None, step=0, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
+        """torch.optim.AdamW with several param_groups in ONE launch: ``table`` = [(end, lr, weight_decay), ...] over the flat buffer
+        (ends increasing, the last = n_train; engine_finetune.adamw_segment_table builds it).  ``state`` (device int32[4]): guarded like
+        adamw_guarded, ``step`` ignored; None: unguarded with the 1-based ``step``.  The table is a host array the library reads during
+        the call only (it travels in the kernel's arguments): nothing to keep alive, no sync."""
+        self._refuse_inference("adamw_segments")
+        if not hasattr(self.L, "dyt_adamw_segments"):
+            raise DyTError("this libdyt_hip has no dyt_adamw_segments (parameter groups): rebuild it")
+        arr = adamw_segment_array(table)
+        with torch.cuda.device(self.device):
+            self._ck(self.L.dyt_adamw_segments(ptr(self.flat), ptr(self.grad), ptr(exp_avg), ptr(exp_avg_sq), self.n_train, ptr(state),
+                                            int(step), ctypes.cast(arr, ctypes.c_void_p), len(table), beta1, beta2, eps, grad_scale,
+                                            stream_ptr()))
 
     def clip_grad_norm(self, max_norm, pre_scale=1.0, norm_out=None):
         """torch.nn.utils.clip_grad_norm_ on the flat gradient (misc.py:262-266); pre_scale = the factor AdamW applies."""

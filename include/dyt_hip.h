@@ -373,6 +373,22 @@ int dyt_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq
 int dyt_adamw_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, int32_t* state,
                       float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
 
+/* The same update for torch.optim.AdamW with several param_groups (the reference's util/lr_decay.py recipe: no weight decay on 1-D tensors,
+ * layer-wise lr): ONE launch over the flat buffer, lr and weight_decay taken per segment.  Segment k covers elements
+ * [segments[k-1].end, segments[k].end), the first starts at 0.  `segments` is a HOST array that is read during the call and never
+ * afterwards (the table travels in the kernel's arguments), so the caller may overwrite it as soon as the call returns; no host sync.
+ *   state != NULL   the guarded semantics above over the WHOLE buffer (an inf / NaN anywhere in grad leaves every segment untouched and
+ *                   is counted in state[1]; the bias corrections use state[0] + 1); `step` is ignored
+ *   state == NULL   the unguarded semantics with the 1-based `step`
+ * Every element sees the arithmetic of the one-group entries bit for bit.  DYT_ERR_ARG (with an error text, before anything is
+ * enqueued): num_segments outside 1 ... DYT_ADAMW_MAX_SEGMENTS, ends that do not increase strictly, a last end other than numel.
+ * Added without an ABI version change (the version stays 5): a caller discovers this entry by its symbol (dlsym / hasattr). */
+#define DYT_ADAMW_MAX_SEGMENTS 128
+typedef struct { int64_t end; float lr; float weight_decay; } dyt_adamw_segment;   /* elements [previous end, end) */
+int dyt_adamw_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
+                       int32_t* state, int step, const dyt_adamw_segment* segments, int num_segments,
+                       float beta1, float beta2, float eps, float grad_scale, void* stream);
+
 /* One whole fine-tune step body (engine_finetune.py:47-79 without the host syncs): student +
  * teacher forward, loss, one backward over both passes into grad_flat (zeroed first).  The caller
  * all-reduces grad_flat (DDP, main_image.py:280-282) and then calls dyt_adamw. */
