@@ -1388,156 +1388,125 @@ __global__ __launch_bounds__(448) void attn_bwd_dkv_split_kernel(const float* __
 }
 
 // ------------------------------------------------------------------------------------------
-static int set_lds(const void* f, size_t bytes) {
-    DYT_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+// The process-wide switches the launchers read (C ABI: dyt_set_option / dyt_set_global_option); copied into the route's shape
+struct AttnSwitches {
+    int f32_split = 0;   // DYT_OPT_F32_SPLIT16: the split forward kernel for every fp32-mode call (unit entries; contexts pass their own flag)
+    int v2 = -1;         // DYT_OPT_ATTN_V2; -1: not set yet -> DYT_ATTN_V2 from the environment (default 3: both round-5 kernels)
+    int bwd_fused = 1;   // DYT_OPT_ATTN_BWD_FUSED
+};
+static AttnSwitches g_attn;
+void set_attn_f32_split(int on) { g_attn.f32_split = on; }
+void set_attn_v2(int mask) { g_attn.v2 = mask; }
+void set_attn_bwd_fused(int on) { g_attn.bwd_fused = on; }
+static int attn_v2_mask() {
+    if (g_attn.v2 < 0) { const char* e = getenv("DYT_ATTN_V2"); g_attn.v2 = e ? (atoi(e) & 3) : 3; }
+    return g_attn.v2;
+}
+
+template <bool PLANES, int PARTS, bool LSE>   // PLANES: the hi planes take the place of the 16-bit copies of q / k / v
+static int launch_fwd_split(const AttnFwdArgs& a, hipStream_t s) {
+    constexpr auto kern = attn_fwd_split_kernel<PLANES, PARTS, LSE>;
+    const int grid = a.batch * NH;
+    const size_t lds = 2 * ROW_IMG + 2 * TR_IMG;
+    if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3(min(grid, 256)), dim3(448), lds, s, (const float*)(PLANES ? nullptr : a.q), (const float*)(PLANES ? nullptr : a.k),
+                       (const float*)(PLANES ? nullptr : a.v), (float*)a.out, LSE ? a.lse : nullptr, grid, (bf16*)a.out3,
+                       (bf16*)(PLANES ? a.q_hi : a.q16), (bf16*)(PLANES ? a.k_hi : a.k16), (bf16*)(PLANES ? a.v_hi : a.v16), (bf16*)a.o16, (int)a.out3_f8,
+                       (const bf16*)(PLANES ? a.q_lo : nullptr), (const bf16*)(PLANES ? a.k_lo : nullptr), (const bf16*)(PLANES ? a.v_lo : nullptr));
+    DYT_HIP_CHECK(hipGetLastError());
     return 0;
 }
-// the attribute belongs to the (kernel, device) pair: one flag per device and kernel family
-static bool* attr_flag(int family) {
-    static bool done[3][64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    return &done[family][dev & 63];
-}
 
-static int g_attn_f32_split = 0;   // process-wide: the split forward kernel for every fp32-mode call (unit entries; contexts pass their own flag)
-void set_attn_f32_split(int on) { g_attn_f32_split = on; }
-
-int launch_attn_fwd(int precision, const void* q, const void* k, const void* v, void* out, float* lse, int batch,
-                    hipStream_t s, int split16, void* out3, const AttnSave16* save16, int out3_f8, int parts) {
-    const int grid = batch * NH;
+int launch_attn_fwd(int precision, const AttnFwdArgs& a, hipStream_t s) {
     if (dbg_skip(2)) return 0;
-    if ((save16 || !out) && !(precision == 0 && (split16 || g_attn_f32_split))) { set_error("attention forward: 16-bit copies / no fp32 output need the split kernel"); return -1; }
-    if (!out && !out3) { set_error("attention forward: no output"); return -1; }
-    if (precision == 0 && (split16 || g_attn_f32_split)) {
-        const size_t lds = 2 * ROW_IMG + 2 * TR_IMG;
-        static bool done[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (!done[dev & 63]) {
-            if (set_lds((const void*)attn_fwd_split_kernel<false>, lds) || set_lds((const void*)attn_fwd_split_kernel<true>, lds) ||
-                set_lds((const void*)attn_fwd_split_kernel<true, 1>, lds) || set_lds((const void*)attn_fwd_split_kernel<false, 3, false>, lds) ||
-                set_lds((const void*)attn_fwd_split_kernel<true, 3, false>, lds) || set_lds((const void*)attn_fwd_split_kernel<true, 1, false>, lds)) return -2;
-            done[dev & 63] = true;
+    AttnFwdShape sh;
+    sh.precision = precision; sh.split = a.split16 || g_attn.f32_split; sh.out = a.out != nullptr; sh.out3 = a.out3 != nullptr; sh.planes = a.planar;
+    sh.saved = a.q16 || a.k16 || a.v16; sh.o16 = a.o16 != nullptr; sh.out3_f8 = a.out3_f8; sh.parts = a.parts; sh.lse_optional = a.lse_optional;
+    sh.v2 = attn_v2_mask();
+    const AttnFwdRoute r = attn_fwd_route(sh);
+    if (r.error) { set_error("%s", r.error); return -1; }
+    if (r.store_lse && !a.lse) { set_error("attention forward: this kernel writes lse"); return -1; }
+    const int grid = a.batch * NH;
+    switch (r.kernel) {
+        case AF_SPLIT_F32: return launch_fwd_split<false, 3, true>(a, s);
+        case AF_SPLIT_P3: return launch_fwd_split<true, 3, true>(a, s);
+        case AF_SPLIT_P1: return launch_fwd_split<true, 1, true>(a, s);
+        case AF_SPLIT_F32_NOSAVE: return launch_fwd_split<false, 3, false>(a, s);
+        case AF_SPLIT_P3_NOSAVE: return launch_fwd_split<true, 3, false>(a, s);
+        case AF_SPLIT_P1_NOSAVE: return launch_fwd_split<true, 1, false>(a, s);
+        case AF_EXACT: {
+            const size_t lds = F_IMG + NPAD * HD * sizeof(float);
+            if (int rc = ensure_dyn_lds<attn_fwd_f32_kernel>(lds)) return rc;
+            hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(grid), dim3(448), lds, s, (const float*)a.q, (const float*)a.k, (const float*)a.v, (float*)a.out, a.lse);
+            break;
         }
-        if (parts != 3 && !(save16 && save16->q_lo && parts == 1)) { set_error("attention forward: the one-part form needs the planar q / k / v"); return -1; }
-        // one-part form with nothing but the operand image to write (every block of a complete_model pass but the cls-only last one): the
-        // round-5 16-bit kernel on the hi planes, its result split on the way out (DYT_OPT_ATTN_V2 bit 0)
-        if (save16 && save16->q_lo && parts == 1 && !out && out3 && out3_f8 && !save16->o && (get_attn_v2() & 1))
-            return launch_attn_fwd_v2(save16->q, save16->k, save16->v, out3, lse, batch, s, 1);
-        // lse == null (inference-only contexts): the no-save variants
-        auto* k_p1 = lse ? attn_fwd_split_kernel<true, 1> : attn_fwd_split_kernel<true, 1, false>;
-        auto* k_p3 = lse ? attn_fwd_split_kernel<true> : attn_fwd_split_kernel<true, 3, false>;
-        auto* k_f32 = lse ? attn_fwd_split_kernel<false> : attn_fwd_split_kernel<false, 3, false>;
-        if (save16 && save16->q_lo && parts == 1)
-            hipLaunchKernelGGL(k_p1, dim3(min(grid, 256)), dim3(448), lds, s, nullptr, nullptr, nullptr, (float*)out, lse, grid,
-                               (bf16*)out3, (bf16*)save16->q, (bf16*)save16->k, (bf16*)save16->v, (bf16*)save16->o, out3_f8,
-                               (const bf16*)save16->q_lo, (const bf16*)save16->k_lo, (const bf16*)save16->v_lo);
-        else if (save16 && save16->q_lo)
-            hipLaunchKernelGGL(k_p3, dim3(min(grid, 256)), dim3(448), lds, s, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)out, lse, grid,
-                               (bf16*)out3, (bf16*)save16->q, (bf16*)save16->k, (bf16*)save16->v, (bf16*)save16->o, out3_f8,
-                               (const bf16*)save16->q_lo, (const bf16*)save16->k_lo, (const bf16*)save16->v_lo);
-        else
-        hipLaunchKernelGGL(k_f32, dim3(min(grid, 256)), dim3(448), lds, s, (const float*)q, (const float*)k,
-                           (const float*)v, (float*)out, lse, grid, (bf16*)out3, save16 ? (bf16*)save16->q : nullptr, save16 ? (bf16*)save16->k : nullptr,
-                           save16 ? (bf16*)save16->v : nullptr, save16 ? (bf16*)save16->o : nullptr, out3_f8, nullptr, nullptr, nullptr);
-    } else if (!lse && !(precision != 0 && (get_attn_v2() & 1))) {   // (the exact-fp32 kernel and the round-4 16-bit kernel have no no-save variant: their callers pass the buffer)
-        set_error("attention forward: this kernel writes lse");
-        return -1;
-    } else if (precision == 0) {
-        if (out3) { set_error("attention forward: split output without the split kernel"); return -1; }
-        const size_t lds = F_IMG + NPAD * HD * sizeof(float);
-        bool* once = attr_flag(0);
-        if (!*once) { if (set_lds((const void*)attn_fwd_f32_kernel, lds)) return -2; *once = true; }
-        hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(grid), dim3(448), lds, s, (const float*)q, (const float*)k,
-                           (const float*)v, (float*)out, lse);
-    } else if (get_attn_v2() & 1) {
-        return launch_attn_fwd_v2(q, k, v, out, lse, batch, s);
-    } else {
-        const size_t lds = ROW_IMG + TR_IMG;
-        hipLaunchKernelGGL(attn_fwd_bf16_kernel, dim3(min(grid, 256)), dim3(448), lds, s, (const bf16*)q, (const bf16*)k,
-                           (const bf16*)v, (bf16*)out, lse, grid);
+        case AF_16:
+            hipLaunchKernelGGL(attn_fwd_bf16_kernel, dim3(min(grid, 256)), dim3(448), ROW_IMG + TR_IMG, s, (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v,
+                               (bf16*)a.out, a.lse, grid);
+            break;
+        default: return launch_attn_fwd_v2(a, r, s);
     }
     DYT_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-static int g_attn_v2 = -1;   // -1: not set yet -> DYT_ATTN_V2 from the environment (default 3: both round-5 kernels)
-void set_attn_v2(int mask) { g_attn_v2 = mask; }
-int get_attn_v2() {
-    if (g_attn_v2 < 0) { const char* e = getenv("DYT_ATTN_V2"); g_attn_v2 = e ? (atoi(e) & 3) : 3; }
-    return g_attn_v2;
+template <bool ROWPF>
+static int launch_bwd_fused(const AttnBwdArgs& a, int out_ld, hipStream_t s) {
+    constexpr auto kern = attn_bwd_fused_bf16_kernel<ROWPF>;
+    const int grid = a.batch * NH;
+    const size_t lds = 2 * ROW_IMG + 2 * TR_IMG + 2 * NPAD * sizeof(float);
+    if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3(min(grid, 256)), dim3(448), lds, s, (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v, (const bf16*)a.out,
+                       (const bf16*)a.dout, a.lse, a.delta, (bf16*)a.dqkv, grid, a.q_tiles, out_ld);
+    DYT_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
-static int g_attn_bwd_fused = 1;   // 16-bit modes: one kernel for dQ and dK/dV (0: the two separate kernels; 2: fused, row prefetch a head ahead)
-void set_attn_bwd_fused(int on) { g_attn_bwd_fused = on; }
-
-int launch_attn_bwd(int precision, const void* q, const void* k, const void* v, const void* out, const void* dout,
-                    const float* lse, float* delta, void* dqkv, int batch, hipStream_t s, int q_tiles, void* dqkv3, float s3, int split16, int grad_parts, int out_hi_only,
-                    int out_ld) {
-    if (out_ld <= 0) out_ld = D;
-    if (out_ld != D && precision == 0) { set_error("attention backward: a strided `out` is a 16-bit-kernel feature"); return -1; }
-    const int grid = batch * NH;
+int launch_attn_bwd(int precision, const AttnBwdArgs& a, hipStream_t s) {
     if (dbg_skip(1)) return 0;
-    if (precision == 0 && (split16 || g_attn_f32_split)) {
-        const size_t lds1 = 4 * ROW_H + 2 * TR_H, lds2 = 4 * ROW_H + 4 * TR_H + 2 * HROWS * sizeof(float);
-        static bool done[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (!done[dev & 63]) {
-            if (set_lds((const void*)attn_bwd_dq_split_kernel<3>, lds1) || set_lds((const void*)attn_bwd_dq_split_kernel<1>, lds1)) return -2;
-            if (set_lds((const void*)attn_bwd_dkv_split_kernel<3>, lds2) || set_lds((const void*)attn_bwd_dkv_split_kernel<1>, lds2)) return -2;
-            done[dev & 63] = true;
+    const int out_ld = a.out_ld > 0 ? a.out_ld : D, grid = a.batch * NH;
+    AttnBwdShape sh;
+    sh.precision = precision; sh.split = a.split16 || g_attn.f32_split; sh.grad_parts = a.grad_parts; sh.out_strided = out_ld != D;
+    sh.v2 = attn_v2_mask(); sh.fused = g_attn.bwd_fused;
+    const AttnBwdRoute r = attn_bwd_route(sh);
+    if (r.error) { set_error("%s", r.error); return -1; }
+    switch (r.kernel) {
+        case AB_SPLIT3: case AB_SPLIT1: {
+            const size_t lds1 = 4 * ROW_H + 2 * TR_H, lds2 = 4 * ROW_H + 4 * TR_H + 2 * HROWS * sizeof(float);
+            if (int rc = ensure_dyn_lds<attn_bwd_dq_split_kernel<3>, attn_bwd_dq_split_kernel<1>>(lds1)) return rc;
+            if (int rc = ensure_dyn_lds<attn_bwd_dkv_split_kernel<3>, attn_bwd_dkv_split_kernel<1>>(lds2)) return rc;
+            auto* kq = r.kernel == AB_SPLIT3 ? attn_bwd_dq_split_kernel<3> : attn_bwd_dq_split_kernel<1>;
+            auto* kkv = r.kernel == AB_SPLIT3 ? attn_bwd_dkv_split_kernel<3> : attn_bwd_dkv_split_kernel<1>;
+            const float gs = a.dqkv3 ? a.s3 : 4096.0f;   // (4096: unit entries, no context)
+            hipLaunchKernelGGL(kq, dim3(min(grid, 256)), dim3(448), lds1, s, (const float*)a.q, (const float*)a.k, (const float*)a.v, (const float*)a.out,
+                               (const float*)a.dout, a.lse, a.delta, (float*)a.dqkv, (bf16*)a.dqkv3, a.s3, grid, gs, (int)a.out_hi_only);
+            hipLaunchKernelGGL(kkv, dim3(min(grid, 256)), dim3(448), lds2, s, (const float*)a.q, (const float*)a.k, (const float*)a.v, (const float*)a.dout,
+                               a.lse, a.delta, (float*)a.dqkv, (bf16*)a.dqkv3, a.s3, grid, gs, (int)a.out_hi_only);
+            break;
         }
-        constexpr float gs_unit = 4096.0f;   // unit entries (no context)
-        auto* kq = grad_parts >= 3 ? attn_bwd_dq_split_kernel<3> : attn_bwd_dq_split_kernel<1>;
-        auto* kkv = grad_parts >= 3 ? attn_bwd_dkv_split_kernel<3> : attn_bwd_dkv_split_kernel<1>;
-        hipLaunchKernelGGL(kq, dim3(min(grid, 256)), dim3(448), lds1, s, (const float*)q, (const float*)k, (const float*)v,
-                           (const float*)out, (const float*)dout, lse, delta, (float*)dqkv, (bf16*)dqkv3, s3, grid, dqkv3 ? s3 : gs_unit, out_hi_only);
-        hipLaunchKernelGGL(kkv, dim3(min(grid, 256)), dim3(448), lds2, s, (const float*)q, (const float*)k, (const float*)v,
-                           (const float*)dout, lse, delta, (float*)dqkv, (bf16*)dqkv3, s3, grid, dqkv3 ? s3 : gs_unit, out_hi_only);
-        DYT_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (precision == 0) {
-        const size_t lds1 = 2 * F_IMG;
-        const size_t lds2 = 2 * F_IMG + 2 * NPAD * sizeof(float);
-        bool* once = attr_flag(1);
-        if (!*once) {
-            if (set_lds((const void*)attn_bwd_dq_f32_kernel, lds1)) return -2;
-            if (set_lds((const void*)attn_bwd_dkv_f32_kernel, lds2)) return -2;
-            *once = true;
+        case AB_EXACT: {
+            const size_t lds1 = 2 * F_IMG, lds2 = 2 * F_IMG + 2 * NPAD * sizeof(float);
+            if (int rc = ensure_dyn_lds<attn_bwd_dq_f32_kernel>(lds1)) return rc;
+            if (int rc = ensure_dyn_lds<attn_bwd_dkv_f32_kernel>(lds2)) return rc;
+            hipLaunchKernelGGL(attn_bwd_dq_f32_kernel, dim3(grid), dim3(448), lds1, s, (const float*)a.q, (const float*)a.k, (const float*)a.v,
+                               (const float*)a.out, (const float*)a.dout, a.lse, a.delta, (float*)a.dqkv, (bf16*)a.dqkv3, a.s3);
+            hipLaunchKernelGGL(attn_bwd_dkv_f32_kernel, dim3(grid), dim3(448), lds2, s, (const float*)a.q, (const float*)a.k, (const float*)a.v,
+                               (const float*)a.dout, a.lse, a.delta, (float*)a.dqkv, (bf16*)a.dqkv3, a.s3);
+            break;
         }
-        hipLaunchKernelGGL(attn_bwd_dq_f32_kernel, dim3(grid), dim3(448), lds1, s, (const float*)q, (const float*)k,
-                           (const float*)v, (const float*)out, (const float*)dout, lse, delta, (float*)dqkv, (bf16*)dqkv3, s3);
-        hipLaunchKernelGGL(attn_bwd_dkv_f32_kernel, dim3(grid), dim3(448), lds2, s, (const float*)q, (const float*)k,
-                           (const float*)v, (const float*)dout, lse, delta, (float*)dqkv, (bf16*)dqkv3, s3);
-    } else {
-        const size_t lds1 = 2 * ROW_IMG + TR_IMG;
-        const size_t lds2 = 2 * ROW_IMG + 2 * TR_IMG + 2 * NPAD * sizeof(float);
-        bool* once = attr_flag(2);
-        if (!*once) {
-            if (set_lds((const void*)attn_bwd_dq_bf16_kernel, lds1)) return -2;
-            if (set_lds((const void*)attn_bwd_dkv_bf16_kernel, lds2)) return -2;
-            if (set_lds((const void*)attn_bwd_fused_bf16_kernel<false>, lds2)) return -2;
-            if (set_lds((const void*)attn_bwd_fused_bf16_kernel<true>, lds2)) return -2;
-            *once = true;
+        case AB_16_TWO: {
+            const size_t lds1 = 2 * ROW_IMG + TR_IMG, lds2 = 2 * ROW_IMG + 2 * TR_IMG + 2 * NPAD * sizeof(float);
+            if (int rc = ensure_dyn_lds<attn_bwd_dq_bf16_kernel>(lds1)) return rc;
+            if (int rc = ensure_dyn_lds<attn_bwd_dkv_bf16_kernel>(lds2)) return rc;
+            hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel, dim3(min(grid, 256)), dim3(448), lds1, s, (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v,
+                               (const bf16*)a.out, (const bf16*)a.dout, a.lse, a.delta, (bf16*)a.dqkv, grid, out_ld);
+            hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel, dim3(min(grid, 256)), dim3(448), lds2, s, (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v,
+                               (const bf16*)a.dout, a.lse, a.delta, (bf16*)a.dqkv, grid);
+            break;
         }
-        if (get_attn_v2() & 2) return launch_attn_bwd_v2(q, k, v, out, dout, lse, dqkv, batch, s, q_tiles, out_ld);
-        if (g_attn_bwd_fused) {
-            if (g_attn_bwd_fused == 2)
-                hipLaunchKernelGGL(attn_bwd_fused_bf16_kernel<true>, dim3(min(grid, 256)), dim3(448), lds2, s, (const bf16*)q, (const bf16*)k,
-                                   (const bf16*)v, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, grid, q_tiles, out_ld);
-            else
-                hipLaunchKernelGGL(attn_bwd_fused_bf16_kernel<false>, dim3(min(grid, 256)), dim3(448), lds2, s, (const bf16*)q, (const bf16*)k,
-                                   (const bf16*)v, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, grid, q_tiles, out_ld);
-            DYT_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-        hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel, dim3(min(grid, 256)), dim3(448), lds1, s, (const bf16*)q, (const bf16*)k,
-                           (const bf16*)v, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, grid, out_ld);
-        hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel, dim3(min(grid, 256)), dim3(448), lds2, s, (const bf16*)q, (const bf16*)k,
-                           (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dqkv, grid);
+        case AB_16_FUSED: return launch_bwd_fused<false>(a, out_ld, s);
+        case AB_16_FUSED_AHEAD: return launch_bwd_fused<true>(a, out_ld, s);
+        default: return launch_attn_bwd_v2(a, s);
     }
     DYT_HIP_CHECK(hipGetLastError());
     return 0;

@@ -659,48 +659,33 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_v2_kernel(const bf16* __restr
 
 }  // namespace av2
 
-static int set_lds_v2(const void* fn, size_t bytes) {
-    DYT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
-int launch_attn_fwd_v2(const void* q, const void* k, const void* v, void* out, float* lse, int batch, hipStream_t s, int out3_f8) {
-    const int grid = batch * NH;
+template <bool OUT3, bool LSE>   // OUT3: on the hi planes; `out3` = the proj GEMM's operand image in the hi16 / fp8 form (rows of SPLIT_A * 768)
+static int launch_fwd_v2(const AttnFwdArgs& a, hipStream_t s) {
+    constexpr auto kern = av2::attn_fwd_v2_kernel<true, 0, OUT3, LSE>;   // (PIPE = false: tools/probes/r5/av2_test.hip only)
+    const int grid = a.batch * NH;
     const size_t lds = 5 * av2::IMG;
-    static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (!done[dev & 63]) {
-        if (set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true>, lds) || set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true>, lds) ||
-            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, false, false>, lds) ||
-            set_lds_v2((const void*)av2::attn_fwd_v2_kernel<true, 0, true, false>, lds)) return -2;
-        done[dev & 63] = true;
-    }
-    if (out3_f8) {   // `out` = the proj GEMM's operand image in the hi16 / fp8 form
-        auto* kern3 = lse ? av2::attn_fwd_v2_kernel<true, 0, true> : av2::attn_fwd_v2_kernel<true, 0, true, false>;   // lse == null: the no-save variant
-        hipLaunchKernelGGL(kern3, dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                           (bf16*)out, lse, grid);
-        DYT_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    auto* kern = lse ? av2::attn_fwd_v2_kernel<true> : av2::attn_fwd_v2_kernel<true, 0, false, false>;   // (PIPE = false: tools/probes/r5/av2_test.hip only)
-    hipLaunchKernelGGL(kern, dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, lse, grid);
+    if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3(min(grid, 256)), dim3(512), lds, s, (const bf16*)(OUT3 ? a.q_hi : a.q), (const bf16*)(OUT3 ? a.k_hi : a.k),
+                       (const bf16*)(OUT3 ? a.v_hi : a.v), (bf16*)(OUT3 ? a.out3 : a.out), LSE ? a.lse : nullptr, grid);
     DYT_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-int launch_attn_bwd_v2(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, void* dqkv,
-                       int batch, hipStream_t s, int q_tiles, int out_ld) {
-    const int grid = batch * NH;
-    static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (!done[dev & 63]) {
-        if (set_lds_v2((const void*)av2::attn_bwd_v2_kernel<0>, av2::BWD_LDS)) return -2;
-        done[dev & 63] = true;
+int launch_attn_fwd_v2(const AttnFwdArgs& a, const AttnFwdRoute& r, hipStream_t s) {
+    switch (r.kernel) {
+        case AF_V2: return launch_fwd_v2<false, true>(a, s);
+        case AF_V2_F8: return launch_fwd_v2<true, true>(a, s);
+        case AF_V2_NOSAVE: return launch_fwd_v2<false, false>(a, s);
+        case AF_V2_F8_NOSAVE: return launch_fwd_v2<true, false>(a, s);
+        default: set_error("attention forward: not a round-5 kernel"); return -1;
     }
-    hipLaunchKernelGGL(av2::attn_bwd_v2_kernel<0>, dim3(min(grid, 256)), dim3(512), av2::BWD_LDS, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                       (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, grid, q_tiles, out_ld);
+}
+
+int launch_attn_bwd_v2(const AttnBwdArgs& a, hipStream_t s) {
+    const int grid = a.batch * NH;
+    if (int rc = ensure_dyn_lds<av2::attn_bwd_v2_kernel<0>>(av2::BWD_LDS)) return rc;
+    hipLaunchKernelGGL(av2::attn_bwd_v2_kernel<0>, dim3(min(grid, 256)), dim3(512), av2::BWD_LDS, s, (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v,
+                       (const bf16*)a.out, (const bf16*)a.dout, a.lse, (bf16*)a.dqkv, grid, a.q_tiles, a.out_ld > 0 ? a.out_ld : D);
     DYT_HIP_CHECK(hipGetLastError());
     return 0;
 }

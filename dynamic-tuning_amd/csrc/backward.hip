@@ -335,9 +335,15 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
             CK("proj_dgrad dO", T.dO, (size_t)M * D * atb);
         }
         POISON(32, T.dqkv, (size_t)M * 3 * D * atb);
-        ISO(1, RUN(1, 14.0 * B * NH * (double)NT * NT * HD,
-            launch_attn_bwd(P, b16 ? L.q16 : L.q, b16 ? L.k16 : L.k, b16 ? L.v16 : L.v, b16 ? L.ao3 : L.attn_o, T.dO, L.lse, T.delta, T.dqkv, B, s, (tail && !student) ? 1 : 7,
-                            split16 ? T.dqkv3 : nullptr, c->split_gs, split16 && c->split_attn, c->split_bwd_attn_parts, c->split_bwd_parts == 1, b16 ? SPLIT_A * D : 0)););   // teacher tail: du, hence dO, is zero off the cls rows
+        {
+            AttnBwdArgs a; a.batch = B; a.q = b16 ? L.q16 : L.q; a.k = b16 ? L.k16 : L.k; a.v = b16 ? L.v16 : L.v;
+            a.out = b16 ? L.ao3 : L.attn_o; a.out_ld = b16 ? SPLIT_A * D : 0;   // bwd16: the hi plane of the proj GEMM's operand image
+            a.dout = T.dO; a.lse = L.lse; a.delta = T.delta; a.dqkv = T.dqkv;
+            a.q_tiles = (tail && !student) ? 1 : 7;   // teacher tail: du, hence dO, is zero off the cls rows
+            a.dqkv3 = split16 ? T.dqkv3 : nullptr; a.s3 = c->split_gs; a.out_hi_only = c->split_bwd_parts == 1;
+            a.split16 = split16 && c->split_attn; a.grad_parts = c->split_bwd_attn_parts;
+            ISO(1, RUN(1, 14.0 * B * NH * (double)NT * NT * HD, launch_attn_bwd(P, a, s)););
+        }
         CK("attn_bwd delta", T.delta, (size_t)B * NH * NT * 4); CK("attn_bwd dqkv", T.dqkv, (size_t)M * 3 * D * atb);
         {
             GemmArgs a; a.A = T.dqkv; a.W = qkv_wT; a.Wp = qkv_wTp; a.M = M; a.N = D; a.K = 3 * D; a.out_at = T.dxn; if (split16) { SPLIT_G(a, W.qkv_wT3); SPLIT_READY(a, T.dqkv3); }

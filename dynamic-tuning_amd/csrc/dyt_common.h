@@ -323,4 +323,18 @@ void set_error(const char* fmt, ...);
         }                                                                                \
     } while (0)
 
+// A kernel that takes more than 64 KB of dynamic LDS needs its limit raised first.  The attribute belongs to the (kernel, device) pair:
+// one flag per device for the kernels named (one kernel, or the instances of one template that share a size), set before the first launch there
+template <auto... Kernels>
+int ensure_dyn_lds(size_t bytes) {
+    static bool done[64] = {};
+    int dev = 0;
+    DYT_HIP_CHECK(hipGetDevice(&dev));
+    if (done[dev & 63]) return 0;
+    const void* const kernels[] = {reinterpret_cast<const void*>(Kernels)...};
+    for (const void* k : kernels) DYT_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done[dev & 63] = true;
+    return 0;
+}
+
 }  // namespace dyt

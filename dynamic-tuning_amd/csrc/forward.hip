@@ -185,8 +185,6 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     // inference-only: what an eval forward stores for the backward alone is not stored -- the launchers take a null pointer
     // as "no-save variant"; values that flow on are computed by the same instructions
     const bool nosave = c->inf;
-    // (the attention kernels with a no-save variant: the split fp32 kernel and the round-5 16-bit kernel; the other two keep their lse store)
-    const bool lse_nosave = nosave && (P == 0 ? (c->split16 && c->split_attn) : (get_attn_v2() & 1) != 0);
     S.valid = false;
     if (B % c->frames != 0) { set_error("video model: batch %d is not a multiple of frames %d", B, c->frames); return DYT_ERR_ARG; }
     if (do_prep) { int rc = prep_adapters(c, trainable, s); if (rc) return rc; rc = prep_pool(c, trainable, s); if (rc) return rc; }
@@ -246,9 +244,17 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
             void* ao3 = (c->split16 && c->split_attn) ? ((save16 && L.ao3) ? L.ao3 : T.g3) : nullptr;   // the split attention kernel also writes the proj GEMM's operand
             // last block of a pass without a gate (teacher / complete model): the proj GEMM runs on the gathered cls rows of the fp32 output
             const bool tail_proj = c->cls_tail && l == depth - 1 && l > 0 && !tokens_out && !use_gate;
-            AttnSave16 sv16{L.q16, L.k16, L.v16, nullptr};   // (the output's 16-bit copy is the hi plane of ao3)
-            if (planes) { sv16.q_lo = T.qlo; sv16.k_lo = T.klo; sv16.v_lo = T.vlo; }   // bwd16: the 16-bit copies the backward reads (the fp32 output is then not needed once the proj operand is written)
-            RUN(1, 4.0 * B * NH * (double)NT * NT * HD, launch_attn_fwd(P, L.q, L.k, L.v, (save16 && ao3 && !tail_proj) ? nullptr : L.attn_o, lse_nosave ? nullptr : L.lse, B, s, c->split16 && c->split_attn, ao3, (save16 || planes) ? &sv16 : nullptr, (fm >> 1) & 1, (planes && (fm & 32)) ? 1 : 3));
+            {
+                AttnFwdArgs a; a.batch = B; a.q = L.q; a.k = L.k; a.v = L.v;
+                a.lse = L.lse; a.lse_optional = nosave;   // (the attention kernels without a no-save variant keep their lse store)
+                a.split16 = c->split16 && c->split_attn; a.out3 = ao3; a.out3_f8 = (fm >> 1) & 1;
+                a.out = (save16 && ao3 && !tail_proj) ? nullptr : L.attn_o;   // bwd16: the fp32 output is not needed once the proj operand is written (its 16-bit copy is the hi plane of ao3)
+                if (planes) {   // the hi planes are also the 16-bit copies the backward reads
+                    a.planar = true; a.q_hi = L.q16; a.k_hi = L.k16; a.v_hi = L.v16; a.q_lo = T.qlo; a.k_lo = T.klo; a.v_lo = T.vlo;
+                    a.parts = (fm & 32) ? 1 : 3;
+                }
+                RUN(1, 4.0 * B * NH * (double)NT * NT * HD, launch_attn_fwd(P, a, s));
+            }
             if (tail_proj) {
                 // last block of a pass without a gate (teacher / complete model): only u[cls] is read downstream (LN2 / MLP / adapter of
                 // the cls rows, their backward) -- the proj GEMM runs on the B gathered cls rows; same k order, same bits for those rows

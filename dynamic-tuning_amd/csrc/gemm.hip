@@ -1110,15 +1110,8 @@ static int launch_bf16_cfg(const GemmArgs& a, const Epi& epi, hipStream_t s, int
     if (m_end <= m_begin) return 0;
     const int grid = tile_grid(m_begin, m_end, a.N, BM, BN);
     const size_t lds = 2 * (BM + BN) * 64 * 2;
-    auto kern = gemm_bf16_nt_kernel<BM, BN, WAVES_M, WAVES_N, Epi, ABL, CAT, F8, LEAD>;
-    static bool attr_set[64] = {};   // per device: the attribute belongs to the (kernel, device) pair
-    int dev = 0;
-    DYT_HIP_CHECK(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        DYT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)lds));
-        attr_set[dev & 63] = true;
-    }
+    constexpr auto kern = gemm_bf16_nt_kernel<BM, BN, WAVES_M, WAVES_N, Epi, ABL, CAT, F8, LEAD>;
+    if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
     const CatArgs cat{static_cast<const bf16*>(a.A2), static_cast<const bf16*>(a.W2), a.a2_map, a.out_scale, a.a_fold, a.a_ld, a.f8_begin, a.w_exp};
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), lds, s, static_cast<const bf16*>(a.A), static_cast<const bf16*>(a.W),
                        m_end, a.N, a.K, a.m_dev, a.a_map, m_begin, epi, cat);
@@ -1213,15 +1206,8 @@ template <int BM, int BN, class Epi>
 static int launch_f32_cfg(const GemmArgs& a, const Epi& epi, hipStream_t s) {
     const int grid = tile_grid(0, a.M, a.N, BM, BN);
     const size_t lds = 2 * (BM + BN) * 128;
-    auto kern = gemm_f32_mfma_nt_kernel<BM, BN, 2, 2, Epi>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    DYT_HIP_CHECK(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        DYT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)lds));
-        attr_set[dev & 63] = true;
-    }
+    constexpr auto kern = gemm_f32_mfma_nt_kernel<BM, BN, 2, 2, Epi>;
+    if (int rc = ensure_dyn_lds<kern>(lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, static_cast<const float*>(a.A), static_cast<const float*>(a.W),
                        a.M, a.N, a.K, a.m_dev, a.a_map, 0, epi);
     DYT_HIP_CHECK(hipGetLastError());

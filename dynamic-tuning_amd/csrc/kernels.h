@@ -2,6 +2,7 @@
 #pragma once
 #include <stdlib.h>
 #include "dyt_common.h"
+#include "attn_route.h"
 
 namespace dyt {
 
@@ -116,31 +117,52 @@ int launch_gemm_f32_raw(const void* A, const void* W, void* C, int M, int N, int
 // ------------------------------------------------------------------------------------------
 // attention (N = 197, d = 64, 12 heads); q pre-scaled by 1/8 in the QKV epilogue
 // ------------------------------------------------------------------------------------------
-// q,k,v: [B*12][197][64] AT ; out: [B*197][768] AT ; lse: [B*12][197] f32
-// 16-bit copies of q / k / v (same layout) and of the output [B*197][768] written by the split forward kernel for a 16-bit backward
-struct AttnSave16 { void* q = nullptr; void* k = nullptr; void* v = nullptr; void* o = nullptr;
-                    // planes: q / k / v above are INPUT hi planes (written by the QKV epilogue) and these the lo planes; the fp32 q / k / v arguments are unused
-                    const void* q_lo = nullptr; const void* k_lo = nullptr; const void* v_lo = nullptr; };
-int launch_attn_fwd(int precision, const void* q, const void* k, const void* v, void* out, float* lse,
-                    int batch, hipStream_t s, int split16 = 0, void* out3 = nullptr, const AttnSave16* save16 = nullptr, int out3_f8 = 0,
-                    int parts = 3);   // parts = 1 (split kernel on planar q / k / v): S and P V as the hi * hi product alone   // out may be null when out3 is given   // out3: + the output as a [M][3*768] split operand   // split16 (fp32 mode): products as three 16-bit MFMA products
-void set_attn_f32_split(int on);   // process-wide version of split16 (unit entries)
-// dqkv: [B*197][2304] AT (dq already multiplied by 1/8) ; delta: scratch [B*12][197] f32
-int launch_attn_bwd(int precision, const void* q, const void* k, const void* v, const void* out,
-                    const void* dout, const float* lse, float* delta, void* dqkv, int batch, hipStream_t s, int q_tiles = 7,
-                    void* dqkv3 = nullptr, float s3 = 1.f, int split16 = 0, int grad_parts = 3, int out_hi_only = 0, int out_ld = 0);   // out_ld: row stride of `out` (0 = 768; 16-bit kernels: the hi plane of a split operand image)   // out_hi_only: dqkv3 without its lo half (the qkv dgrad contracts one part)
-      // split16 (fp32 mode): the split backward kernels; grad_parts = 1: their dP / dQ / dK / dV products as hi * hi alone   // dqkv3 (fp32 mode): dqkv * s3 as split 16-bit operand [M, 3 * 2304] instead of fp32
-// q_tiles: 32-row query tiles that can carry a non-zero dout (1: only the cls rows do); honoured by the fused 16-bit kernel, exact
-// 16-bit modes: 1 (default) = dQ and dK/dV of a head in one persistent kernel, 0 = the two separate kernels (process-wide)
-void set_attn_bwd_fused(int on);
-// round-5 kernels (attention_v2.hip; 16-bit modes): bit 0 = forward (online softmax, LDS-DMA images, two workgroups per CU), bit 1 = backward
+// The kernel is chosen by attn_fwd_route() / attn_bwd_route() (attn_route.h) from these fields and the three process-wide switches
+struct AttnFwdArgs {
+    const void* q = nullptr; const void* k = nullptr; const void* v = nullptr;   // [B*12][197][64] AT
+    // planar form (split kernel): q / k / v as the 16-bit hi + lo planes the QKV epilogue wrote; q / k / v above are unused
+    bool planar = false;
+    const void* q_hi = nullptr; const void* k_hi = nullptr; const void* v_hi = nullptr;
+    const void* q_lo = nullptr; const void* k_lo = nullptr; const void* v_lo = nullptr;
+    void* out = nullptr;      // [B*197][768] AT; may be null when out3 is given
+    void* out3 = nullptr;     // + the output as a [M][SPLIT_A*768] split operand (split kernel)
+    bool out3_f8 = false;     // ... in the hi16 / fp8 form
+    // 16-bit copies for a 16-bit backward, written by the split kernel: of the fp32 q / k / v (same layout; not in the planar form, whose
+    // hi planes are those copies) and of the output [B*197][768]
+    void* q16 = nullptr; void* k16 = nullptr; void* v16 = nullptr; void* o16 = nullptr;
+    float* lse = nullptr;        // [B*12][197] f32, always a buffer
+    bool lse_optional = false;   // the caller does not read lse (inference-only contexts): a kernel with a no-save variant skips the store
+    bool split16 = false;        // fp32 mode: products as three 16-bit MFMA products (the split kernel)
+    int parts = 3;               // 1 (planar form): S and P V as the hi * hi product alone
+    int batch = 0;
+};
+struct AttnBwdArgs {
+    const void* q = nullptr; const void* k = nullptr; const void* v = nullptr;   // as the forward's
+    const void* out = nullptr;    // [B*197][out_ld] AT
+    int out_ld = 0;               // row stride of `out` (0 = 768; 16-bit kernels: the hi plane of a split operand image)
+    const void* dout = nullptr;   // [B*197][768] AT
+    const float* lse = nullptr;
+    float* delta = nullptr;       // scratch [B*12][197] f32
+    void* dqkv = nullptr;         // [B*197][2304] AT (dq already multiplied by 1/8)
+    void* dqkv3 = nullptr;        // fp32 mode: dqkv * s3 as split 16-bit operand [M, 3 * 2304] instead of fp32
+    float s3 = 1.f;
+    bool out_hi_only = false;     // dqkv3 without its lo half (the qkv dgrad contracts one part)
+    bool split16 = false;         // fp32 mode: the split backward kernels
+    int grad_parts = 3;           // 1: their dP / dQ / dK / dV products as hi * hi alone
+    int q_tiles = 7;              // 32-row query tiles that can carry a non-zero dout (1: only the cls rows do); fused 16-bit kernels
+    int batch = 0;
+};
+int launch_attn_fwd(int precision, const AttnFwdArgs& a, hipStream_t s);
+int launch_attn_bwd(int precision, const AttnBwdArgs& a, hipStream_t s);
+// the round-5 kernels' side of the two launchers above (attention_v2.hip): r.kernel is one of AF_V2* / the route is AB_V2
+int launch_attn_fwd_v2(const AttnFwdArgs& a, const AttnFwdRoute& r, hipStream_t s);
+int launch_attn_bwd_v2(const AttnBwdArgs& a, hipStream_t s);
+// process-wide switches (attention.hip: AttnSwitches)
+void set_attn_f32_split(int on);   // DYT_OPT_F32_SPLIT16: split16 for every fp32-mode call (unit entries)
+void set_attn_bwd_fused(int on);   // DYT_OPT_ATTN_BWD_FUSED, 16-bit modes: 1 (default) = dQ and dK/dV of a head in one persistent kernel, 0 = the two separate kernels, 2 = fused, row prefetch a head ahead
+void set_attn_v2(int mask);        // DYT_OPT_ATTN_V2, 16-bit modes: bit 0 = the round-5 forward kernel, bit 1 = the backward one
 void set_gemm_splitk(int on);   // DYT_OPT_GEMM_SPLITK
 int get_gemm_splitk();
-void set_attn_v2(int mask);
-int get_attn_v2();
-int launch_attn_fwd_v2(const void* q, const void* k, const void* v, void* out, float* lse, int batch, hipStream_t s, int out3_f8 = 0);   // out3_f8: `out` is the proj GEMM's operand image in the hi16 / fp8 form (rows of SPLIT_A * 768)
-int launch_attn_bwd_v2(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, void* dqkv,
-                       int batch, hipStream_t s, int q_tiles, int out_ld);
 
 // ------------------------------------------------------------------------------------------
 // row-wise / small kernels

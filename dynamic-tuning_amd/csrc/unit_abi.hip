@@ -137,7 +137,8 @@ static int attention_test(const float* qkv, float* out, const float* dout, float
     if (!q || !k || !v || !o || !lse) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
     const size_t n3 = M * 3 * D;
     hipLaunchKernelGGL(qkv_split_kernel<AT>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, qkv, q, k, v, B);
-    int rc = launch_attn_fwd(P, q, k, v, o, lse, B, s);
+    AttnFwdArgs f; f.batch = B; f.q = q; f.k = k; f.v = v; f.out = o; f.lse = lse;
+    int rc = launch_attn_fwd(P, f, s);
     if (rc) return rc;
     hipLaunchKernelGGL(to_f32_kernel<AT>, dim3((unsigned)((M * D + 255) / 256)), dim3(256), 0, s, (const AT*)o, out, M * D);
     if (dout && dqkv) {
@@ -145,7 +146,8 @@ static int attention_test(const float* qkv, float* out, const float* dout, float
         float* delta = (float*)sc.get((size_t)B * NH * NT * 4);
         if (!d_o || !dq || !delta) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
         rc = launch_convert(P, dout, d_o, (int64_t)(M * D), s); if (rc) return rc;
-        rc = launch_attn_bwd(P, q, k, v, o, d_o, lse, delta, dq, B, s); if (rc) return rc;
+        AttnBwdArgs b; b.batch = B; b.q = q; b.k = k; b.v = v; b.out = o; b.dout = d_o; b.lse = lse; b.delta = delta; b.dqkv = dq;
+        rc = launch_attn_bwd(P, b, s); if (rc) return rc;
         hipLaunchKernelGGL(to_f32_kernel<AT>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, (const AT*)dq, dqkv, n3);
     }
     DYT_HIP_CHECK(hipGetLastError());

@@ -38,7 +38,9 @@ int main(int argc, char** argv) {
     hipMemcpy(dk, k.data(), q.size() * 2, hipMemcpyHostToDevice);
     hipMemcpy(dv, v.data(), q.size() * 2, hipMemcpyHostToDevice);
     hipMemset(dout, 0xff, (size_t)B * NT * D * 2);
-    int rc = launch_attn_fwd_v2(dq, dk, dv, dout, dlse, B, 0);
+    AttnFwdArgs fa; fa.q = dq; fa.k = dk; fa.v = dv; fa.out = dout; fa.lse = dlse; fa.batch = B;
+    const AttnFwdRoute fr{AF_V2, true, nullptr};
+    int rc = launch_attn_fwd_v2(fa, fr, 0);
     hipError_t e = hipDeviceSynchronize();
     printf("launch rc %d sync %s\n", rc, hipGetErrorString(e));
     {   // determinism: repeat the forward launch and compare bitwise
@@ -46,7 +48,7 @@ int main(int argc, char** argv) {
         hipMemcpy(o0.data(), dout, o0.size() * 2, hipMemcpyDeviceToHost);
         for (int rep = 0; rep < 8; ++rep) {
             hipMemset(dout, 0xff, (size_t)B * NT * D * 2);
-            if (rep < 4) launch_attn_fwd_v2(dq, dk, dv, dout, dlse, B, 0);
+            if (rep < 4) launch_attn_fwd_v2(fa, fr, 0);
             else hipLaunchKernelGGL((av2::attn_fwd_v2_kernel<false, 0>), dim3(nh), dim3(512), 5 * av2::IMG, 0, dq, dk, dv, dout, dlse, nh);
             hipDeviceSynchronize();
             hipMemcpy(o1.data(), dout, o1.size() * 2, hipMemcpyDeviceToHost);
@@ -200,7 +202,8 @@ int main(int argc, char** argv) {
         hipMemcpy(ddo, dO.data(), dO.size() * 2, hipMemcpyHostToDevice);
         hipMemset(dg, 0xff, (size_t)B * NT * 3 * D * 2);
         const int nqt = argc > 4 ? atoi(argv[4]) : 7;
-        int rcb = launch_attn_bwd_v2(dq, dk, dv, dout, ddo, dlse, dg, B, 0, nqt, D);
+        AttnBwdArgs ba; ba.q = dq; ba.k = dk; ba.v = dv; ba.out = dout; ba.dout = ddo; ba.lse = dlse; ba.dqkv = dg; ba.batch = B; ba.q_tiles = nqt;
+        int rcb = launch_attn_bwd_v2(ba, 0);
         hipError_t eb = hipDeviceSynchronize();
         printf("bwd launch rc %d sync %s\n", rcb, hipGetErrorString(eb));
         std::vector<bf16> g((size_t)B * NT * 3 * D);
