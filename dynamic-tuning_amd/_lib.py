@@ -25,6 +25,7 @@ PREC_FP16F8 = 6   # host-side name only: PREC_FP16X3H with the forward GEMMs' co
 PREC_FP16X3Q = 7  # host-side name only: PREC_FP16X3H with the attention branch's GEMMs (qkv, proj) in the fp8-correction form, the MLP three-part (DYT_OPT_F32_SPLIT16 = 5)
 PREC_FP16X3 = 3   # host-side name only: libdyt_hip_f16.so in its fp32 mode with DYT_OPT_F32_SPLIT16 (frozen-weight GEMMs as three IEEE-half products)
 F_TRAINING, F_COMPLETE, F_SAVE, F_MASKED_DENSE, F_GATE_ALWAYS, F_ACCUM_GRAD, F_DEVICE_SEED, F_TOKENS_IN, F_TOKENS_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256
+F_IMAGES_U8, F_IMAGES_NHWC = 512, 1024   # `images` is a uint8 batch, normalised in the patch-embedding load; ... in channels-last layout
 CREATE_WIDE_HEAD = 1   # dyt_ctx_create_ex: DYT_CREATE_WIDE_HEAD (the head on the MFMA kernels of csrc/head_wide.hip, up to 65 536 classes)
 CREATE_AVG_POOL = 2    # DYT_CREATE_AVG_POOL: global_pool='avg' -- the head reads the mean of the 196 patch rows (given together with CREATE_FC_NORM)
 CREATE_FC_NORM = 4     # DYT_CREATE_FC_NORM: the head's LayerNorm is the trainable fc_norm of the flat buffer, the final norm an identity
@@ -146,6 +147,74 @@ def wide_head_default(explicit=None, tuning_config=None, num_classes=0):
     return int(num_classes) > 1024
 
 
+INPUT_NORMS = {"imagenet": ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225)),   # timm IMAGENET_DEFAULT_MEAN / _STD
+               "inception": ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5))}                     # the reference's --inception switch
+
+
+def input_norm_default(explicit=None, tuning_config=None):
+    """The models' ``input_norm`` keyword: the explicit value, else ``tuning_config.dyt_input_norm``, else None (off: uint8 inputs are
+    converted with ``.float()`` as raw 0..255 values).  A value is ``(mean, std)`` (three numbers each) or one of the names of INPUT_NORMS;
+    returned as a tuple of two 3-tuples of floats.  With it set, uint8 batches stay bytes up to the patch-embedding load."""
+    v = explicit
+    if v is None:
+        try:
+            v = getattr(tuning_config, "dyt_input_norm")
+        except (AttributeError, KeyError):
+            v = None
+    if v is None or v is False:
+        return None
+    if isinstance(v, str):
+        if v.lower() not in INPUT_NORMS:
+            raise ValueError("input_norm=%r: a (mean, std) pair or one of %s" % (v, sorted(INPUT_NORMS)))
+        v = INPUT_NORMS[v.lower()]
+    mean, std = v
+    mean, std = tuple(float(x) for x in mean), tuple(float(x) for x in std)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("input_norm: mean and std have three components each (got %r, %r)" % (mean, std))
+    import math
+    if not all(math.isfinite(x) for x in mean) or not all(math.isfinite(x) and x > 0 for x in std):
+        raise ValueError("input_norm: mean must be finite, std finite and > 0 (got %r, %r)" % (mean, std))
+    return mean, std
+
+
+def float3(values):
+    """Three numbers as the host float[3] the input-norm entries read during the call."""
+    return (ctypes.c_float * 3)(*[float(x) for x in values])
+
+
+def byte_image_layout(t, lead=1):
+    """None unless ``t`` is a uint8 image batch; else "nchw" for [..., 3, 224, 224] and "nhwc" for [..., 224, 224, 3] behind ``lead``
+    leading dimensions (the shape decides the layout)."""
+    import torch
+    if t.dtype != torch.uint8:
+        return None
+    tail = tuple(t.shape[lead:])
+    if tail == (3, 224, 224):
+        return "nchw"
+    if tail == (224, 224, 3):
+        return "nhwc"
+    raise DyTError("uint8 images must be [B,3,224,224] or [B,224,224,3] (got shape %s)" % (tuple(t.shape),))
+
+
+def normalize_u8(images, mean, std, out=None):
+    """dyt_normalize_u8: a uint8 device batch [B,3,224,224] / [B,224,224,3] -> fp32 [B,3,224,224], ((u / 255) - mean) / std in three fp32
+    operations (ToTensor + Normalize), on torch's current stream."""
+    import torch
+    layout = byte_image_layout(images)
+    if layout is None:
+        raise DyTError("normalize_u8 takes uint8 images (got %s)" % images.dtype)
+    L = lib()
+    if not hasattr(L, "dyt_normalize_u8"):
+        raise DyTError("this libdyt_hip has no dyt_normalize_u8 (byte images): rebuild it")
+    images = images.contiguous()
+    B = images.shape[0]
+    if out is None:
+        out = torch.empty(B, 3, 224, 224, device=images.device, dtype=torch.float32)
+    with torch.cuda.device(images.device):
+        check(L.dyt_normalize_u8(ptr(images), ptr(out), B, 1 if layout == "nhwc" else 0, float3(mean), float3(std), stream_ptr()), L)
+    return out
+
+
 _lib = None
 
 _vp, _i, _i64, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
@@ -164,6 +233,8 @@ SYMBOLS = {
     "dyt_set_drop_path": (_i, [_vp, _f]),
     "dyt_set_drop_path_scales": (_i, [_vp, _i, _vp]),
     "dyt_set_soft_targets": (_i, [_vp, _vp, _i]),
+    "dyt_set_input_norm": (_i, [_vp, ctypes.POINTER(_f), ctypes.POINTER(_f)]),
+    "dyt_normalize_u8": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
     "dyt_trainable_numel": (_i, [_vp, ctypes.POINTER(_i64)]),
     "dyt_trainable_offset": (_i, [_vp, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
@@ -209,7 +280,7 @@ SYMBOLS = {
 
 # Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
-OPTIONAL_SYMBOLS = {"dyt_adamw_segments"}
+OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8"}
 
 _lib16 = None
 

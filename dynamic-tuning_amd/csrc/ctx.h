@@ -211,6 +211,7 @@ struct dyt_ctx {
     float* ad_up_bp = nullptr;   // [depth][768] s * up_proj.bias (prep_adapters_kernel)
     float* ad_lift = nullptr;    // [2][depth] 2^e / 2^-e of the 16-bit up_proj dgrad operand (adapter_lift_kernel)
     float drop_path_rate = 0.f;  // timm DropPath rate of the LAST block (block l: rate * l / (depth - 1)); training forward passes only
+    InputNorm in_norm = IN_NORM_IMAGENET;   // dyt_set_input_norm: per-channel mean / std of DYT_F_IMAGES_U8 passes (host values, carried in the launch arguments)
     int count_flops_tokens = 0;  // > 0: Block.forward_count_flops -- MLP on the first n tokens of every image
     // profiling
     bool prof = false;

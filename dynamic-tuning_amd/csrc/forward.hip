@@ -124,6 +124,8 @@ int dyt::branch_stream(dyt_ctx* c, Slot& S, hipStream_t* out) {
     return 0;
 }
 
+static_assert(IN_F_TOKENS_IN == DYT_F_TOKENS_IN && IN_F_IMAGES_U8 == DYT_F_IMAGES_U8 && IN_F_IMAGES_NHWC == DYT_F_IMAGES_NHWC, "input_norm.h flag values");
+
 static inline void* at_off(const dyt_ctx* c, void* base, size_t elems) { return static_cast<char*>(base) + elems * c->at; }
 
 // ------------------------------------------------------------------------------------------
@@ -167,6 +169,7 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     if (B < 1 || B > c->cfg.max_batch) { set_error("batch %d exceeds max_batch %d", B, c->cfg.max_batch); return DYT_ERR_ARG; }
     if (!images || !trainable || !logits) { set_error("null argument"); return DYT_ERR_ARG; }
     if ((g1 == nullptr) != (g2 == nullptr)) { set_error("g1 and g2 must be given together"); return DYT_ERR_ARG; }
+    { int rc = check_image_input(flags, images); if (rc) return rc; }   // DYT_F_IMAGES_U8 / _NHWC: `images` is a byte batch
     if (flags & DYT_F_SAVE) { int rc = refuse_inference(c, slot > 0 ? "dyt_forward with DYT_F_SAVE into a slot > 0" : "dyt_forward with DYT_F_SAVE"); if (rc) return rc; }
     if ((flags & DYT_F_TRAINING) && c->drop_path_rate > 0.f) { int rc = refuse_inference(c, "a training forward with stochastic depth"); if (rc) return rc; }
     const int P = c->prec, depth = c->cfg.depth, M = B * NT, r = c->cfg.ffn_num;
@@ -210,7 +213,10 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
         DYT_HIP_CHECK(hipMemcpyAsync(S.xs[0], images, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else if (!share0) {
         // patch embedding: im2col + GEMM (+bias +pos_embed), cls rows
-        RUN(2, 0, launch_im2col(P, images, T.xn, B, s));
+        if (flags & DYT_F_IMAGES_U8)   // bytes, normalised in the load: the same operand bits as the float path on the normalised image
+            RUN(2, 0, launch_im2col_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, s));
+        else
+            RUN(2, 0, launch_im2col(P, images, T.xn, B, s));
         {
             GemmArgs a; a.A = T.xn; a.W = c->pe_w; a.M = B * NP; a.N = D; a.K = D;
             a.bias = c->pe_b; a.pos = c->pos; a.out_f32 = S.xs[0]; SPLIT(a, c->pe_w3);

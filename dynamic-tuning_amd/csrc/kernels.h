@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include "dyt_common.h"
 #include "attn_route.h"
+#include "input_norm.h"
 
 namespace dyt {
 
@@ -222,6 +223,10 @@ int launch_ln_cls(int precision, const float* u, const float* w, const float* b,
 int launch_cls_index(int* cls_rows, int batch, hipStream_t s);
 
 int launch_im2col(int precision, const float* images, void* out, int batch, hipStream_t s);
+// input_u8.hip: the same operand from a uint8 batch ([B,3,224,224], nhwc: [B,224,224,3]), normalised with nm in the load; and the plain fp32 image
+int launch_im2col_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, hipStream_t s);
+int launch_normalize_u8(const uint8_t* src, float* dst, int batch, int nhwc, const InputNorm& nm, hipStream_t s);
+int check_image_input(int flags, const void* images);   // DYT_F_IMAGES_U8 / _NHWC of a pass: flag combination and pointer alignment, DYT_ERR_ARG with a text
 int launch_cls_rows(const float* cls, const float* pos, float* x0, int batch, hipStream_t s);
 // fp32 -> AT copy (n elements)
 int launch_convert(int precision, const float* src, void* dst, int64_t n, hipStream_t s);

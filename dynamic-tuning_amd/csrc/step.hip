@@ -94,7 +94,8 @@ extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* 
                                 float* logits_t, float* token_select, void* stream) {
     if (!c) { set_error("null argument"); return DYT_ERR_ARG; }
     { int rc = refuse_inference(c, "dyt_step_fwd_bwd"); if (rc) return rc; }
-    if (!targets || !grad_flat || !out_losses) { set_error("null argument"); return DYT_ERR_ARG; }
+    if (!images || !targets || !grad_flat || !out_losses) { set_error("null argument"); return DYT_ERR_ARG; }
+    { int rc = check_image_input(flags, images); if (rc) return rc; }   // byte images: refused here, before the step enqueues anything
     if (c->cfg.slots < 2) { set_error("dyt_step_fwd_bwd needs 2 slots"); return DYT_ERR_STATE; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int depth = c->cfg.depth;
@@ -102,7 +103,8 @@ extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* 
     const size_t kz = (size_t)depth * batch * NT * c->cfg.ffn_num;
     float* ls = logits_s ? logits_s : c->logits_s;
     float* lt = logits_t ? logits_t : c->logits_t;
-    const int fl = (flags & (DYT_F_MASKED_DENSE | DYT_F_DEVICE_SEED)) | DYT_F_TRAINING | DYT_F_SAVE;
+    // (the image flags reach both passes: the teacher's own embedding, when block 0 is not shared, reads the same bytes)
+    const int fl = (flags & (DYT_F_MASKED_DENSE | DYT_F_DEVICE_SEED | DYT_F_IMAGES_U8 | DYT_F_IMAGES_NHWC)) | DYT_F_TRAINING | DYT_F_SAVE;
     // Two-stream schedule: student pass on the caller's stream, teacher pass on a side stream
     // (fork/join with events; graph-capturable).  Profiling mode runs serially for clean per-kernel times.
     const bool par = c->overlap && c->ov_pass && !c->prof;

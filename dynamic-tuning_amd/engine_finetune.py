@@ -519,7 +519,7 @@ def train_step(model, samples, targets, optimizer, criterion=None, losses_out=No
     m = getattr(model, "module", model)
     if getattr(m, "inference_only", False):
         raise DyTError("train_step: the model was built with inference_only (eval forwards only); build it without inference_only to train")
-    samples = m.fold_input(samples.float()).contiguous()   # video: [b,c,t,h,w] -> [(b t),c,h,w]
+    samples = m.prepare_input(samples)   # video: [b,c,t,h,w] -> [(b t),c,h,w]; uint8 batches of a model with input_norm stay bytes
     eng = m.engine(samples.shape[0], samples.device)
     # nn.CrossEntropyLoss(label_smoothing = e) is the soft form with t (1 - e) + e / C (torch applies the same map to class-probability targets)
     smooth = float(getattr(getattr(criterion, "base_criterion", None), "label_smoothing", 0.0) or 0.0)
@@ -653,7 +653,7 @@ def _copy_stream_picker(model, criterion, masked=None):
     def pick(samples, targets):
         if samples is None:   # only what is already known
             return getattr(getattr(m, "_engine", None), "_copy_stream_probe", (None, None))[0]
-        x = m.fold_input(samples.float()).contiguous()
+        x = m.prepare_input(samples)
         eng = m.engine(x.shape[0], x.device)
         if not hasattr(eng, "_copy_stream_probe"):
             scratch = torch.zeros(8, device=x.device)
@@ -709,6 +709,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         if it % accum_iter == 0:   # per-iteration schedule, reference :43-46
             lr = lr_sched.adjust_learning_rate(optimizer, it / nsteps + epoch, args)
         if mixup_fn is not None:   # reference :44-45 (timm.data.Mixup or any callable of that shape): mixed samples, class-probability targets
+            if m.takes_bytes(samples):   # timm's Mixup multiplies in place: it gets the fp32 images the byte path would compute with (dyt_normalize_u8)
+                samples = m.bytes_to_float(samples)
             samples, targets = mixup_fn(samples, targets)
         train_step(model, samples, targets, optimizer, criterion, losses_out=step_losses, seed=step_seed(epoch, it),
                    gumbel=gumbel, keep_mask=keep_mask, accumulate=(it % accum_iter != 0), update=((it + 1) % accum_iter == 0),

@@ -13,7 +13,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from _lib import DyTError, OPT_COUNT_FLOPS_TOKENS, inference_only_default, key_to_param, wide_head_default, is_trainable_param
+from _lib import DyTError, OPT_COUNT_FLOPS_TOKENS, inference_only_default, input_norm_default, key_to_param, wide_head_default, is_trainable_param
 from runtime import DyTEngine, parse_precision
 from .dynamic_adapter import Adapter, TokenSelect, _LinearParams
 
@@ -189,7 +189,7 @@ class VisionTransformer(nn.Module):
                  no_embed_class=False, pre_norm=False, fc_norm=None, drop_rate=0., pos_drop_rate=0., patch_drop_rate=0.,
                  proj_drop_rate=0., attn_drop_rate=0., drop_path_rate=0., weight_init='', embed_layer=None,
                  norm_layer=None, act_layer=None, block_fn=Block, mlp_layer=None, tuning_config=None, select_config=None,
-                 precision=None, max_batch=None, train_mode=None, inference_only=None, wide_head=None):
+                 precision=None, max_batch=None, train_mode=None, inference_only=None, wide_head=None, input_norm=None):
         super().__init__()
         fixed = dict(img_size=(img_size, 224), patch_size=(patch_size, 16), in_chans=(in_chans, 3), embed_dim=(embed_dim, 768),
                      num_heads=(num_heads, 12), mlp_ratio=(mlp_ratio, 4.0), qkv_bias=(qkv_bias, True),
@@ -257,6 +257,11 @@ class VisionTransformer(nn.Module):
         # wide_head (keyword, else tuning_config.dyt_wide_head, else env DYT_WIDE_HEAD, else num_classes > 1024): the head on the library's
         # MFMA kernels (DYT_CREATE_WIDE_HEAD, up to 65 536 classes: --nb_classes 21843) instead of the row kernels (up to 1024)
         self.wide_head = wide_head_default(wide_head, tuning_config, num_classes)
+        # input_norm (keyword, else tuning_config.dyt_input_norm, else off): (mean, std), "imagenet" or "inception" (the reference's --inception,
+        # 0.5 / 0.5).  With it a uint8 batch [B,3,224,224] or [B,224,224,3] (the shape decides) stays bytes on the bus and in device memory
+        # and is normalised -- ToTensor() + Normalize(mean, std), bit for bit -- where the patch embedding loads it (DYT_F_IMAGES_U8).  Float
+        # inputs are untouched by it; without it a uint8 input is converted with .float() as raw 0..255 values, as before.
+        self.input_norm = input_norm_default(input_norm, tuning_config)
         self._engine = None
         self._sync_state = None
         self._seed_counter = 0
@@ -265,6 +270,21 @@ class VisionTransformer(nn.Module):
     def fold_input(self, x):
         """Image model: the batch is the input itself (the video subclass folds clips into frames here)."""
         return x
+
+    def takes_bytes(self, x):
+        """True when ``x`` goes to the library as uint8: the model was built with ``input_norm`` and ``x`` is a uint8 tensor."""
+        return self.input_norm is not None and x.dtype == torch.uint8
+
+    def prepare_input(self, x):
+        """What every entry does to its image argument: fold clips to frames (video) and make it contiguous -- on the bytes when the
+        model takes them, else after ``.float()``."""
+        return self.fold_input(x if self.takes_bytes(x) else x.float()).contiguous()
+
+    def bytes_to_float(self, x):
+        """A uint8 batch as the fp32 images the byte path computes with (dyt_normalize_u8), in the float layout of this model's input:
+        for whatever must see float images before the library does (a ``mixup_fn``)."""
+        from _lib import normalize_u8
+        return normalize_u8(x, *self.input_norm)
 
     def init_weights(self, m):  # reference :323-332
         if isinstance(m, _LinearParams):
@@ -304,6 +324,8 @@ class VisionTransformer(nn.Module):
                             wide_head=self.wide_head, avg_pool=self.global_pool == 'avg', fc_norm=self.use_fc_norm)
             self._engine = eng
             self._sync_state = None
+        if self.input_norm is not None and eng.input_norm != self.input_norm:
+            eng.set_input_norm(*self.input_norm)
         if not self.inference_only and getattr(eng, "drop_path_rate", 0.0) != self.drop_path_rate:   # (stochastic depth: training passes only)
             eng.set_drop_path(self.drop_path_rate)
         self._sync(eng)
@@ -344,6 +366,7 @@ class VisionTransformer(nn.Module):
     # ---- reference API ------------------------------------------------------------------------
     def forward(self, x, complete_model=False, gumbel=None, keep_mask=None):
         """x [B,3,224,224] -> (logits [B,C], {"token_select": [B,12,196,1], "token_logits": [B,12,196,1]}).
+        With ``input_norm`` x may be uint8, [B,3,224,224] or [B,224,224,3]: raw pixels, normalised inside the patch embedding.
 
         ``gumbel=(g1, g2)`` ([depth,B,196] each) and ``keep_mask`` ([depth,B*197,r] uint8) inject the
         training-mode random draws (parity tests); by default they come from the on-device Philox
@@ -351,7 +374,7 @@ class VisionTransformer(nn.Module):
         if not x.is_cuda:
             raise DyTError("DyT VisionTransformer runs on a HIP device only (input is on %s); there is no CPU path" % x.device)
         self._refuse_training("forward")
-        x = self.fold_input(x.float()).contiguous()
+        x = self.prepare_input(x)
         eng = self.engine(x.shape[0], x.device)
         # FLOP-probe variant (reference Block.forward_count_flops :167-185, set through
         # `model.apply(lambda m: setattr(m, "count_flops", True))` / `token_select_num` as block_flops_dict.get_block_flops
@@ -393,7 +416,7 @@ class VisionTransformer(nn.Module):
         if self._frames and self._frames > 1:
             raise NotImplementedError("forward_features of the video model: its head pools every frame's tokens inside the fused forward")
         self._refuse_training("forward_features", grad_check=False)
-        x = self.fold_input(x.float()).contiguous()
+        x = self.prepare_input(x)
         eng = self.engine(x.shape[0], x.device)
         g1 = g2 = None
         if gumbel is not None:

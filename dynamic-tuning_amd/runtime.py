@@ -10,8 +10,8 @@ import ctypes
 import torch
 
 from _lib import (CREATE_AVG_POOL, CREATE_FC_NORM, CREATE_WIDE_HEAD, Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
-                  F_TRAINING, OPT_F32_SPLIT16, OPT_LEARNABLE_SCALE, PREC_BF16, PREC_FP16, PREC_FP16X3, PREC_FP16F8, PREC_FP16X3F, PREC_FP16X3H, PREC_FP16X3Q, PREC_FP32,
-                  adamw_segment_array, check, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
+                  F_TRAINING, F_IMAGES_NHWC, F_IMAGES_U8, OPT_F32_SPLIT16, OPT_LEARNABLE_SCALE, PREC_BF16, PREC_FP16, PREC_FP16X3, PREC_FP16F8, PREC_FP16X3F, PREC_FP16X3H, PREC_FP16X3Q, PREC_FP32,
+                  INPUT_NORMS, adamw_segment_array, byte_image_layout, check, float3, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
 
 NP, NT, DIM = 196, 197, 768
 
@@ -107,6 +107,7 @@ class DyTEngine:
         self.depth, self.num_classes, self.ffn_num = int(depth), int(num_classes), int(ffn_num)
         # power of two the gradient carries wherever the library holds it in 16 bits (IEEE-half builds: 2^12, dyt_ctx::gs); None: no scaling
         self.grad_scale_log2 = 12 if self.precision in (PREC_FP16, PREC_FP16X3H, PREC_FP16F8, PREC_FP16X3Q) else None
+        self.input_norm = INPUT_NORMS["imagenet"]   # what the context normalises uint8 images with (set_input_norm); the library's default
 
     def _ck(self, rc):
         check(rc, self.L)
@@ -167,12 +168,31 @@ class DyTEngine:
             if n is not None and n != batch:
                 raise DyTError("injected drop-path factors of slot %d are for %d images, this pass has %d" % (sl, n, batch))
 
+    # ---- byte images ------------------------------------------------------------------------
+    def set_input_norm(self, mean, std):
+        """dyt_set_input_norm: per-channel mean / std of the uint8 image batches of the passes enqueued from now on (host values that
+        travel in the kernels' arguments: nothing is launched).  Captured steps are keyed by the values they were captured with."""
+        if not hasattr(self.L, "dyt_set_input_norm"):
+            raise DyTError("this libdyt_hip has no dyt_set_input_norm (byte images): rebuild it")
+        mean, std = tuple(float(x) for x in mean), tuple(float(x) for x in std)
+        self._ck(self.L.dyt_set_input_norm(self.h, float3(mean), float3(std)))
+        self.input_norm = (mean, std)
+
+    def _image_flags(self, images):
+        """DYT_F_IMAGES_U8 (| DYT_F_IMAGES_NHWC) for a uint8 batch [B,3,224,224] / [B,224,224,3] (the shape decides), 0 for float images."""
+        layout = byte_image_layout(images)
+        if layout is None:
+            return 0
+        if not hasattr(self.L, "dyt_set_input_norm"):
+            raise DyTError("this libdyt_hip has no byte-image path (DYT_F_IMAGES_U8): rebuild it")
+        return F_IMAGES_U8 | (F_IMAGES_NHWC if layout == "nhwc" else 0)
+
     # ---- passes -----------------------------------------------------------------------------
     def forward(self, images, slot=0, training=False, complete_model=False, save=False, masked_dense=False,
                 gate_always=False, g1=None, g2=None, keep_mask=None, seed=0, want_tokens=True, trainable=None):
         B = images.shape[0]
         flags = ((F_TRAINING if training else 0) | (F_COMPLETE if complete_model else 0) | (F_SAVE if save else 0) |
-                 (F_MASKED_DENSE if masked_dense else 0) | (F_GATE_ALWAYS if gate_always else 0))
+                 (F_MASKED_DENSE if masked_dense else 0) | (F_GATE_ALWAYS if gate_always else 0) | self._image_flags(images))
         logits = torch.empty(B // self.frames, self.num_classes, device=self.device, dtype=torch.float32)
         has_tok = want_tokens and (not complete_model or gate_always)
         ts = torch.zeros(B, self.depth, NP, device=self.device, dtype=torch.float32) if has_tok else None
@@ -208,7 +228,7 @@ class DyTEngine:
         token_select [B,depth,196], token_logits [B,depth,196])."""
         B = images.shape[0]
         flags = ((F_TRAINING if training else 0) | (F_COMPLETE if complete_model else 0) | (F_MASKED_DENSE if masked_dense else 0) |
-                 F_GATE_ALWAYS | F_TOKENS_OUT)
+                 F_GATE_ALWAYS | F_TOKENS_OUT | self._image_flags(images))
         if training:
             self._dp_check((0,), B)
         out = torch.empty(B, NT, DIM, device=self.device, dtype=torch.float32)
@@ -246,7 +266,8 @@ class DyTEngine:
         self._dp_check((0, 1), B)
         for i in range(len(self.generation)):
             self.generation[i] += 1
-        flags = (F_MASKED_DENSE if masked_dense else 0) | (F_ACCUM_GRAD if accumulate else 0) | (F_DEVICE_SEED if device_seed else 0)
+        flags = ((F_MASKED_DENSE if masked_dense else 0) | (F_ACCUM_GRAD if accumulate else 0) | (F_DEVICE_SEED if device_seed else 0) |
+                 self._image_flags(images))
         out = self.losses if losses is None else losses
         with torch.cuda.device(self.device):
             self._ck(self.L.dyt_step_fwd_bwd(self.h, ptr(images), ptr(targets), B, flags, ptr(self.flat), ptr(g1), ptr(g2),
@@ -267,8 +288,10 @@ class DyTEngine:
         becoming launch-bound).  Inputs are copied into static device buffers; the Philox seed lives on the device
         (DYT_F_DEVICE_SEED) and is set from `seed` before every replay, exactly the value an eager step with the same `seed` uses."""
         self._refuse_inference("step_graph")
-        key = (tuple(images.shape), tuple(targets.shape), float(target_ratio), float(loss_ratio), float(token_minimal),
-               float(token_minimal_weight), bool(masked_dense), bool(accumulate))
+        # (a float batch and a byte batch of one shape are two graphs, so are the two byte layouts -- their shapes differ -- and a byte
+        # step is captured with the input norm of its time)
+        key = (tuple(images.shape), images.dtype, self.input_norm if images.dtype == torch.uint8 else None, tuple(targets.shape),
+               float(target_ratio), float(loss_ratio), float(token_minimal), float(token_minimal_weight), bool(masked_dense), bool(accumulate))
         ent = self._graphs.get(key)
         cur = torch.cuda.current_stream(self.device)
         if ent is None:

@@ -33,17 +33,23 @@ def main():
     ap.add_argument("--keep", type=float, default=0.7, help="target keep ratio of the deterministic (eval) gate")
     ap.add_argument("--no-calibrate", action="store_true",
                     help="leave the gate biases at logit(keep) (the eval gate then keeps whatever fraction has a positive logit)")
+    ap.add_argument("--input", choices=("float", "u8", "u8-nhwc"), default="float",
+                    help="float: normalised fp32 images (the reference's loader output); u8 / u8-nhwc: raw uint8 pixels [B,3,224,224] / "
+                         "[B,224,224,3], normalised inside the patch embedding (the model is built with --input_norm)")
+    ap.add_argument("--input_norm", default="imagenet", help="statistics of the byte path: imagenet or inception")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     tuning = Cfg(ffn_adapt=True, ffn_option="parallel", ffn_adapter_layernorm_option="none",
                  ffn_adapter_init_option="lora", ffn_adapter_scalar="0.1", ffn_num=args.ffn_num, d_model=768)
     model = vit_base_patch16_224_in21k(num_classes=args.nb_classes, drop_path_rate=0.0, tuning_config=tuning,
                                        select_config=Cfg(open=True, keep_layers=0), precision=args.precision,
-                                       max_batch=args.batch_size)
+                                       max_batch=args.batch_size, input_norm=None if args.input == "float" else args.input_norm)
     model.load_state_dict(synth.make_state_dict(args.nb_classes, args.ffn_num, kind="bench",
                                                 gate_bias=math.log(args.keep / (1 - args.keep))))
     model = model.to(dev).eval()
     x, _ = synth.make_batch(args.batch_size, args.nb_classes, seed=0)
+    if args.input != "float":   # byte batches go to the model unconverted
+        x = synth.make_byte_batch(args.batch_size, seed=0, nhwc=args.input == "u8-nhwc")
     x = x.to(dev)
     if not args.no_calibrate:
         # the reference learns the keep ratio; the harness pins it: shift every block's gate bias so that the target quantile

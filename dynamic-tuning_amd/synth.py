@@ -194,6 +194,20 @@ def make_batch(batch, num_classes=100, seed=0):
     return x, torch.from_numpy(y.astype(np.int64))
 
 
+def make_byte_batch(batch, seed=0, nhwc=False):
+    """Raw uint8 images [B,3,224,224] (``nhwc``: the same pixels as [B,224,224,3]): in every channel of every image all 256 byte values
+    occur (the first 256 pixels, shuffled into place with the rest), the remainder is uniform random -- so a byte path sees its whole
+    3 x 256 value table on any batch."""
+    g = _rng("byte_images", seed)
+    n = 224 * 224
+    u = g.integers(0, 256, size=(batch, 3, n), dtype=np.uint8)
+    u[:, :, :256] = np.arange(256, dtype=np.uint8)
+    u = np.take_along_axis(u, np.argsort(g.random((batch, 3, n)), axis=2), axis=2).reshape(batch, 3, 224, 224)
+    if nhwc:
+        u = u.transpose(0, 2, 3, 1)
+    return torch.from_numpy(np.ascontiguousarray(u))
+
+
 def mixup_batch(x, y, num_classes, lam=0.7, smoothing=0.1):
     """What timm.data.Mixup(mixup_alpha > 0, label_smoothing) hands the training loop (reference engine_finetune.py:44-45), with a fixed mixing
     weight instead of a Beta draw: samples lam x + (1 - lam) x.flip(0), class-probability targets lam t(y) + (1 - lam) t(y.flip(0)) with

@@ -63,7 +63,16 @@ class VisionTransformer(_ImageViT):
         self._frames = None   # fixed by the first clip tensor (the reference reads t from the input, :436)
 
     def fold_input(self, x):
-        """[b,c,t,h,w] -> [(b t),c,h,w] frames, clip-major (reference :437)."""
+        """[b,c,t,h,w] -> [(b t),c,h,w] frames, clip-major (reference :437).  uint8 clips of a model with ``input_norm`` are folded as
+        bytes: [b,3,t,224,224] -> [(b t),3,224,224], channels-last [b,t,224,224,3] -> [(b t),224,224,3] (the shape decides)."""
+        if x.dim() == 5 and self.takes_bytes(x) and tuple(x.shape[2:]) == (224, 224, 3):
+            b, t = x.shape[:2]
+            if t < 2:
+                raise DyTError("the video model needs t >= 2 frames per clip; use models.vision_transformer_IN21K for images")
+            if self._frames is not None and t != self._frames and self._engine is not None:
+                self._engine = None
+            self._frames = t
+            return x.reshape(b * t, 224, 224, 3).contiguous()
         if x.dim() != 5:
             raise DyTError("the video model takes clips [b,c,t,h,w] (got shape %s)" % (tuple(x.shape),))
         b, c, t, h, w = x.shape
@@ -73,6 +82,13 @@ class VisionTransformer(_ImageViT):
             self._engine = None   # frames per clip changed: the library context is rebuilt
         self._frames = t
         return x.permute(0, 2, 1, 3, 4).reshape(b * t, c, h, w).contiguous()
+
+    def bytes_to_float(self, x):
+        """uint8 clips -> fp32 clips [b,3,t,224,224] (the frames through dyt_normalize_u8)."""
+        from _lib import normalize_u8
+        b = x.shape[0]
+        frames = normalize_u8(self.fold_input(x), *self.input_norm)
+        return frames.reshape(b, frames.shape[0] // b, 3, 224, 224).permute(0, 2, 1, 3, 4)
 
 
 def vit_base_patch16_224_in21k(**kwargs):

@@ -69,6 +69,14 @@ extern "C" {
 #define DYT_F_TOKENS_OUT 256   /* dyt_forward: `logits` receives the block stack's output tokens [B,197,768] (no final norm / head) */
 #define DYT_F_GATE_ALWAYS 16   /* also evaluate the token dispatcher in a COMPLETE pass (the reference does,
                                   and discards it, :150-152) so token_select/token_logits are returned */
+#define DYT_F_IMAGES_U8 512    /* dyt_forward, dyt_step_fwd_bwd: `images` is a `const uint8_t*` batch [B,3,224,224] of raw 0..255 pixels, 16-byte
+                                  aligned.  The patch embedding normalises it in its load: ((float)u / 255.0f - mean[c]) / std[c], three
+                                  correctly rounded fp32 operations -- torchvision's ToTensor() + Normalize(mean, std) -- with the
+                                  context's statistics (dyt_set_input_norm; ImageNet until it is called).  From the embedding GEMM's
+                                  operand onwards the pass is bit for bit the float pass on that normalised image, in every precision
+                                  mode.  Both passes of dyt_step_fwd_bwd read the bytes.  Not with DYT_F_TOKENS_IN (DYT_ERR_ARG). */
+#define DYT_F_IMAGES_NHWC 1024 /* with DYT_F_IMAGES_U8 only (else DYT_ERR_ARG): the byte batch is channels-last, [B,224,224,3] -- what
+                                  image decoders produce */
 
 /* parameter ids (frozen unless marked T = trainable); `layer` is the block index, or 0 */
 enum dyt_param {
@@ -301,6 +309,20 @@ int dyt_set_drop_path(dyt_ctx* ctx, float rate);
  * drawn; the pointer is kept, not copied; null restores the library's own draws. */
 int dyt_set_drop_path_scales(dyt_ctx* ctx, int slot, const float* scales);
 
+/* Byte images (DYT_F_IMAGES_U8).  Added without an ABI version change (the version stays 5): a caller discovers the two entries by
+ * their symbols, like dyt_adamw_segments.
+ * dyt_set_input_norm: the per-channel mean / std of the passes enqueued from now on (the reference's Normalize(mean, std); its
+ * --inception switch is 0.5 / 0.5).  Until it is called a context holds the ImageNet statistics (0.485, 0.456, 0.406) /
+ * (0.229, 0.224, 0.225).  `mean` and `std` are HOST arrays read during the call; the context keeps host values that travel in the
+ * kernels' arguments, so nothing is launched and a step in flight is not disturbed.  A captured step keeps the values it was
+ * captured with.  DYT_ERR_ARG: a non-finite mean, a std component that is not finite and > 0. */
+int dyt_set_input_norm(dyt_ctx* ctx, const float mean[3], const float std[3]);
+/* The same three operations to a plain fp32 image batch, without a context: src uint8 [batch,3,224,224] (nhwc != 0: [batch,224,224,3]),
+ * dst fp32 [batch,3,224,224], both device pointers, 16-byte aligned; mean / std host arrays.  For whatever has to see float images
+ * before the library does (a mixup_fn), and the reference point of the byte path: dyt_forward on bytes equals dyt_forward on this
+ * image bit for bit.  One launch on `stream`, no synchronisation.  DYT_ERR_ARG as above, for a misaligned pointer and for batch < 1. */
+int dyt_normalize_u8(const uint8_t* src, float* dst, int batch, int nhwc, const float mean[3], const float std[3], void* stream);
+
 /* Copy one FROZEN parameter (fp32, reference state_dict layout) into the context; the library
  * keeps its own copies in the layouts/dtypes its kernels want (incl. transposes for dgrad).
  * Replaces load_state_dict(...) for the frozen keys -- main_image.py:245. */
@@ -314,7 +336,7 @@ int dyt_trainable_offset(const dyt_ctx* ctx, int param, int layer, int64_t* offs
 /* VisionTransformer.forward(x, complete_model) -- models/vision_transformer_IN21K.py:343-385,
  * Block.forward :144-165, TokenSelect.forward / _gumbel_sigmoid dynamic_adapter.py:25-77,
  * Adapter.forward :120-140.
- *   images        [B,3,224,224] fp32
+ *   images        [B,3,224,224] fp32, already normalised; with DYT_F_IMAGES_U8 a uint8 batch (see the flag)
  *   trainable     flat trainable buffer (dyt_trainable_offset layout)
  *   g1, g2        [depth,B,196] fp32 Gumbel draws to inject (parity tests), or NULL: logistic noise
  *                 from the on-device Philox stream (seed, slot) -- same distribution as g1-g2
