@@ -219,6 +219,15 @@ _lib = None
 
 _vp, _i, _i64, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
 
+
+class UnitTokBwdArgs(ctypes.Structure):
+    """dyt_unit_tok_bwd_args (include/dyt_hip.h): TokBwdArgs of csrc/kernels.h as a plain C struct; unset pointers are NULL."""
+    _fields_ = [(n, _vp) for n in ("du", "dA2", "dst_of", "u", "stats2", "ln2_w", "gate_w", "soft", "maskf", "dmask", "dtoken_select",
+                                   "dtoken_logits", "dtok", "du_at", "dad", "g_cls", "cat_dact", "cat_ddz", "cat_ddz_dscale", "du3",
+                                   "branch_scale", "du_in_at")] + \
+               [(n, ctypes.c_int32) for n in ("out_stride", "training", "M", "write_du", "du3_hi_only")] + \
+               [(n, _f) for n in ("tau", "gs", "cat_scale", "cat_ddz_scale", "du3_scale")]
+
 # every symbol include/dyt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dyt_last_error": (ctypes.c_char_p, []),
@@ -265,6 +274,10 @@ SYMBOLS = {
     "dyt_mlp_gathered_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "dyt_mlp_gathered_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "dyt_gate_compact": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dyt_unit_bwd_prep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
+    "dyt_unit_ln_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _vp]),
+    "dyt_unit_ln_param_grad": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
+    "dyt_unit_tok_bwd": (_i, [ctypes.POINTER(UnitTokBwdArgs), _vp, _i, _vp]),
     "dyt_gemm_bf16_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_gemm_f32_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_wgrad_scratch_floats": (ctypes.c_int64, [_i]),
@@ -280,7 +293,8 @@ SYMBOLS = {
 
 # Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
-OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8"}
+OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8",
+                    "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
 
 _lib16 = None
 

@@ -508,3 +508,105 @@ extern "C" int dyt_gate_compact(const float* u, const float* w, const float* b, 
     DYT_HIP_CHECK(hipStreamSynchronize(s));
     return DYT_OK;
 }
+
+// ---- the backward row kernels alone (rowops.hip: bwd_prep, ln_bwd, ln_param_grad / ln_param_reduce, tok_bwd + the deferred gate-gradient
+// ---- reduction): argument checks, the product's own launch_* function, synchronise.  Test-only (tests/test_gpu_row_bwd.py). ----
+static int unit_precision_ok(const char* who, int precision) {
+    if (precision == 0 || precision == 1) return 0;
+    set_error("%s: precision %d (0 = fp32, 1 = the library's 16-bit operand type)", who, precision);
+    return DYT_ERR_ARG;
+}
+
+extern "C" int dyt_unit_bwd_prep(const float* g, const void* h, const int32_t* dst_of, const float* row_mask, void* g_at, void* dH,
+                                 float* dmask, int M, float gs, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_bwd_prep", precision); if (rc) return rc; }
+    if (!g || M < 1) { set_error("dyt_unit_bwd_prep: g is NULL or M = %d < 1", M); return DYT_ERR_ARG; }
+    if (!g_at && !dH && !dmask) { set_error("dyt_unit_bwd_prep: no output (g_at, dH and dmask are all NULL)"); return DYT_ERR_ARG; }
+    if (!(gs > 0.f)) { set_error("dyt_unit_bwd_prep: gs = %g (> 0)", gs); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BwdPrepArgs a; a.g = g; a.h = h; a.dst_of = dst_of; a.row_mask = row_mask; a.g_at = g_at; a.dH = dH; a.dmask = dmask; a.M = M; a.gs = gs;
+    int rc = launch_bwd_prep(precision, a, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_ln_bwd(const void* dy, const float* x, const float* stats, const float* w, const float* base, const void* base_at,
+                               float* dx, int rows, void* g_at, const void* h_next, const int32_t* dst_of_next, float* dmask_next, float gs,
+                               void* out3, float s3, int out3_hi_only, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_bwd", precision); if (rc) return rc; }
+    if (!dy || !x || !stats || !w || rows < 1) { set_error("dyt_unit_ln_bwd: dy / x / stats / w is NULL or rows = %d < 1", rows); return DYT_ERR_ARG; }
+    if (!dx && !g_at && !out3) { set_error("dyt_unit_ln_bwd: no output row (dx, g_at and out3 are all NULL)"); return DYT_ERR_ARG; }
+    if (out3 && precision != 0) { set_error("dyt_unit_ln_bwd: out3 (the split operand) exists at precision 0 only"); return DYT_ERR_ARG; }
+    if (base_at && precision == 0) { set_error("dyt_unit_ln_bwd: base_at (the 16-bit stream) exists at precision 1 only"); return DYT_ERR_ARG; }
+    if (base && base_at) { set_error("dyt_unit_ln_bwd: base and base_at are alternatives"); return DYT_ERR_ARG; }
+    if (!(gs > 0.f)) { set_error("dyt_unit_ln_bwd: gs = %g (> 0)", gs); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_ln_bwd(precision, dy, x, reinterpret_cast<const float2*>(stats), w, base, dx, rows, g_at, h_next, dst_of_next, dmask_next, gs, s,
+                           out3, s3, out3_hi_only, base_at);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_ln_param_grad(const void* dy, const float* x, const float* stats, float* out, int rows, float gs, int precision,
+                                      void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_param_grad", precision); if (rc) return rc; }
+    if (!dy || !x || !stats || !out || rows < 1) { set_error("dyt_unit_ln_param_grad: dy / x / stats / out is NULL or rows = %d < 1", rows); return DYT_ERR_ARG; }
+    if (!(gs > 0.f)) { set_error("dyt_unit_ln_param_grad: gs = %g (> 0)", gs); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    float* partial = (float*)sc.get((size_t)ln_param_grad_scratch_floats(rows) * sizeof(float));
+    if (!partial) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+    int rc = launch_ln_param_grad(precision, dy, x, reinterpret_cast<const float2*>(stats), partial, out, rows, gs, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_tok_bwd(const dyt_unit_tok_bwd_args* p, float* d_gate, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_tok_bwd", precision); if (rc) return rc; }
+    if (!p) { set_error("dyt_unit_tok_bwd: args is NULL"); return DYT_ERR_ARG; }
+    if (p->M < NT || p->M % NT != 0) { set_error("dyt_unit_tok_bwd: M = %d is not a positive multiple of %d (the kernel takes image = token / %d)", p->M, NT, NT); return DYT_ERR_ARG; }
+    const bool wr = p->write_du != 0, lnpart = p->dA2 && wr;
+    if (wr && !p->du && !p->du_at) { set_error("dyt_unit_tok_bwd: write_du without du or du_at"); return DYT_ERR_ARG; }
+    if (wr && !p->g_cls && !p->du && !p->du_in_at) { set_error("dyt_unit_tok_bwd: write_du without an incoming gradient (du, du_in_at or g_cls)"); return DYT_ERR_ARG; }
+    if (p->du3 && precision != 0) { set_error("dyt_unit_tok_bwd: du3 (the split operand) exists at precision 0 only"); return DYT_ERR_ARG; }
+    if (p->du_in_at && precision == 0) { set_error("dyt_unit_tok_bwd: du_in_at (the 16-bit stream) exists at precision 1 only"); return DYT_ERR_ARG; }
+    if (precision == 0 && p->gs != 1.0f) { set_error("dyt_unit_tok_bwd: gs = %g at precision 0 (fp32 operands carry no factor)", p->gs); return DYT_ERR_ARG; }
+    if (!(p->gs > 0.f)) { set_error("dyt_unit_tok_bwd: gs = %g (> 0)", p->gs); return DYT_ERR_ARG; }
+    if ((p->dA2 || p->gate_w) && !p->u) { set_error("dyt_unit_tok_bwd: u is NULL (read for the LN2 backward and the gate gradient)"); return DYT_ERR_ARG; }
+    if (lnpart && (!p->stats2 || !p->ln2_w)) { set_error("dyt_unit_tok_bwd: dA2 without stats2 / ln2_w"); return DYT_ERR_ARG; }
+    if (p->gate_w) {
+        if (!p->soft || !d_gate) { set_error("dyt_unit_tok_bwd: gate_w without soft / d_gate"); return DYT_ERR_ARG; }
+        if (p->training && !(p->tau > 0.f)) { set_error("dyt_unit_tok_bwd: tau = %g (> 0)", p->tau); return DYT_ERR_ARG; }
+        if (((p->dtok && !p->dtoken_select) || p->cat_dact) && !p->maskf) { set_error("dyt_unit_tok_bwd: dtok / cat_dact without maskf"); return DYT_ERR_ARG; }
+        if ((p->dtoken_select || p->dtoken_logits) && p->out_stride < NP) { set_error("dyt_unit_tok_bwd: out_stride = %d < %d", p->out_stride, NP); return DYT_ERR_ARG; }
+        if ((p->cat_dact != nullptr) != (p->cat_ddz != nullptr)) { set_error("dyt_unit_tok_bwd: cat_dact and cat_ddz come together"); return DYT_ERR_ARG; }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Scratch sc;
+    const int nblk_max = (p->M + 31) / 32;
+    float* partial = (float*)sc.get((size_t)nblk_max * (D + 1) * sizeof(float));
+    if (!partial) { set_error("scratch alloc failed"); return DYT_ERR_HIP; }
+    TokBwdArgs a;
+    a.du = p->du; a.dA2 = p->dA2; a.dst_of = p->dst_of; a.u = p->u; a.stats2 = reinterpret_cast<const float2*>(p->stats2); a.ln2_w = p->ln2_w;
+    a.gate_w = p->gate_w; a.soft = p->soft; a.maskf = p->maskf; a.dmask = p->dmask;
+    a.dtoken_select = p->dtoken_select; a.dtoken_logits = p->dtoken_logits; a.dtok = p->dtok; a.out_stride = p->out_stride;
+    a.training = p->training; a.tau = p->tau; a.du_at = p->du_at; a.partial = partial; a.M = p->M; a.write_du = wr ? 1 : 0;
+    a.gs = p->gs; a.inv_gs = 1.0f / p->gs; a.dad = p->dad; a.g_cls = p->g_cls;
+    a.cat_dact = p->cat_dact; a.cat_ddz = p->cat_ddz; a.cat_scale = p->cat_scale; a.cat_ddz_scale = p->cat_ddz_scale; a.cat_ddz_dscale = p->cat_ddz_dscale;
+    a.du3 = p->du3; a.du3_scale = p->du3_scale; a.du3_hi_only = p->du3_hi_only != 0;
+    a.branch_scale = p->branch_scale; a.du_in_at = p->du_in_at;
+    int nblk = 0;
+    int rc = launch_tok_bwd(precision, a, &nblk, s);
+    if (rc) return rc;
+    if (nblk > nblk_max) { set_error("dyt_unit_tok_bwd: %d workgroups for %d partial rows", nblk, nblk_max); return DYT_ERR_STATE; }
+    if (p->gate_w) {   // the production path of the gate gradient: queued, then flushed (reduce_partials_batch_kernel)
+        ReduceQueue rq;
+        rc = queue_tok_reduce(rq, partial, nblk, d_gate); if (rc) return rc;
+        rc = flush_reductions(rq, s); if (rc) return rc;
+    }
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}

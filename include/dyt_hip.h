@@ -499,6 +499,54 @@ int dyt_mlp_gathered_fwd(dyt_ctx* ctx, int layer, const float* u, const float* m
  * models/model_speed_test.py:297-305.  Unit-test entry: recomputes the forward, allocates scratch and synchronises. */
 int dyt_mlp_gathered_bwd(dyt_ctx* ctx, int layer, const float* u, const float* mask, const float* dy, float* du, int batch, void* stream);
 
+/* ---- the backward row kernels alone (csrc/rowops.hip), for tests/test_gpu_row_bwd.py.  Each entry checks its arguments (DYT_ERR_ARG with
+ * a text, before anything is enqueued), launches the product's own kernel through the launcher csrc/backward.hip calls, and synchronises.
+ * Added without an ABI version change (the version stays 5), discovered by their symbols like dyt_adamw_segments.
+ * `precision` is DYT_PREC_FP32 or DYT_PREC_BF16; at 1 every `void*` operand is of the library's 16-bit type (bfloat16 in libdyt_hip.so,
+ * IEEE half in libdyt_hip_f16.so), at 0 it is fp32.  gs (> 0) is the factor the 16-bit gradient operands carry (fp16 mode: 2^12, else
+ * 1); the launchers of the first three entries ignore it at precision 0.  `stats` is [rows] (mean, rstd) pairs, i.e. 2 * rows floats.
+ * Buffer sizes are the caller's business: nothing here can check them. */
+/* bwd_prep_kernel (BwdPrepArgs): g_at[t] = AT(gs g[t]); r = dst_of ? dst_of[t] : t; for r >= 0: dH[r] = AT(gs row_mask[t] g[t]) and
+ * dmask[t] = <g[t], h[r]>; dmask[t] = 0 where r < 0 or h is NULL.  g [M,768] fp32; h, dst_of, row_mask, g_at, dH, dmask may each be
+ * NULL (not all three outputs). */
+int dyt_unit_bwd_prep(const float* g, const void* h, const int32_t* dst_of, const float* row_mask, void* g_at, void* dH, float* dmask,
+                      int M, float gs, int precision, void* stream);
+/* ln_bwd_kernel (launch_ln_bwd): d = LNbwd(dy[row] / gs; x[row], stats[row], w) + (base[row] | base_at[row] / gs | 0), written as
+ * dx[row] (fp32), g_at[row] = AT(gs d), out3[row] = d * s3 as the [rows][2*768] hi | lo split operand (precision 0 only; out3_hi_only:
+ * the hi half alone), and dmask_next[row] = <d, h_next[r]> with r = dst_of_next ? dst_of_next[row] : row (0 where r < 0 or h_next is
+ * NULL).  dx may alias base.  base_at: precision 1 only, not together with base.  At least one of dx / g_at / out3. */
+int dyt_unit_ln_bwd(const void* dy, const float* x, const float* stats, const float* w, const float* base, const void* base_at, float* dx,
+                    int rows, void* g_at, const void* h_next, const int32_t* dst_of_next, float* dmask_next, float gs, void* out3,
+                    float s3, int out3_hi_only, int precision, void* stream);
+/* ln_param_grad_kernel + ln_param_reduce_kernel (launch_ln_param_grad; scratch allocated inside): out[0:768] += sum_t (dy[t] / gs) xhat[t],
+ * out[768:1536] += sum_t dy[t] / gs, xhat = (x - mean) rstd from `stats`. */
+int dyt_unit_ln_param_grad(const void* dy, const float* x, const float* stats, float* out, int rows, float gs, int precision, void* stream);
+/* tok_bwd_kernel (launch_tok_bwd) and, with gate_w set, the deferred reduction of its partials (queue_tok_reduce + flush_reductions:
+ * reduce_partials_batch_kernel) into d_gate[769] (+=: 768 weight gradients, then the bias gradient).  The struct mirrors TokBwdArgs of
+ * csrc/kernels.h field for field (its `partial` scratch is allocated inside, inv_gs is 1 / gs); every pointer may be NULL unless
+ * named below.  Per token t = b * 197 + n, with r = the token's compact row (g_cls: b for n == 0, else none; dst_of ? dst_of[t] : t):
+ *   du'  = (g_cls ? (n == 0 ? g_cls[b] : 0) : du_in_at ? du_in_at[t] / gs : du[t]) + dad[t] / gs
+ *          + (r >= 0 ? branch_scale[b] LNbwd(dA2[r]; u[t], stats2[t], ln2_w) / gs : 0) + (n >= 1 && gate_w ? dlogit gate_w : 0)
+ *   dlogit = (branch_scale[b] (dmask[t] - [maskf[t] != 0] <cat_dact[t], cat_ddz[t]> cat_ddz_scale *cat_ddz_dscale) + ext)
+ *            soft[t] (1 - soft[t]) (/ tau when training) + dtoken_logits[b * out_stride + n - 1]
+ *   ext  = dtoken_select ? dtoken_select[b * out_stride + n - 1] : dtok ? dtok[0] + (maskf[t] != 0 ? dtok[2] : dtok[1]) : 0
+ *   d_gate[0:768] += sum_t dlogit u[t], d_gate[768] += sum_t dlogit            (patch tokens only)
+ * du' goes to du (fp32, in place), du_at = AT(gs du') and du3 = du' du3_scale as the split operand -- only when write_du.
+ * DYT_ERR_ARG: M not a positive multiple of 197; write_du with du == NULL and du_at == NULL, or without any incoming gradient; du3 at
+ * precision 1; du_in_at at precision 0; gs != 1 at precision 0; u NULL with dA2 or gate_w; dA2 (with write_du) without stats2 / ln2_w;
+ * gate_w without soft / d_gate, with training and tau <= 0, with dtok or cat_dact but no maskf, with cat_dact xor cat_ddz. */
+typedef struct {
+    float* du; const void* dA2; const int32_t* dst_of; const float* u; const float* stats2; const float* ln2_w;
+    const float* gate_w; const float* soft; const float* maskf; const float* dmask;
+    const float* dtoken_select; const float* dtoken_logits; const float* dtok;
+    void* du_at; const void* dad; const float* g_cls;
+    const void* cat_dact; const void* cat_ddz; const float* cat_ddz_dscale;
+    void* du3; const float* branch_scale; const void* du_in_at;
+    int32_t out_stride, training, M, write_du, du3_hi_only;
+    float tau, gs, cat_scale, cat_ddz_scale, du3_scale;
+} dyt_unit_tok_bwd_args;
+int dyt_unit_tok_bwd(const dyt_unit_tok_bwd_args* args, float* d_gate, int precision, void* stream);
+
 /* One nn.Linear (c = a w^T + bias; a [M,K], w [N,K], bias [N] or NULL, c [M,N], fp32 device pointers) through the split forms of the
  * fp32 mode: form 3 = every product as three IEEE-half products (hi*hi + hi*lo + lo*hi), form 8 = hi*hi on the f16 matrix cores plus
  * the two correction products on the fp8 (e4m3) matrix cores ("fp16f8").  K % 128 == 0, N % 128 == 0.  Unit-test entry: allocates
