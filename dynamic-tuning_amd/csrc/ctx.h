@@ -124,7 +124,7 @@ struct dyt_ctx {
     // (layout / layout_aux); every entry point that needs more refuses (refuse_inference)
     bool inf = false;
     // DYT_CREATE_WIDE_HEAD (dyt_ctx_create_ex): the head runs on the MFMA kernels of head_wide.hip (num_classes up to 65 536) instead of the row
-    // kernels of rowops.hip (up to 1024, the bit-pinned default); image model only
+    // kernels of step_tail.hip (up to 1024, the bit-pinned default); image model only
     bool wide_head = false;
     // DYT_CREATE_FC_NORM: the head's LayerNorm is the reference's fc_norm -- gamma / beta are trainable words of the caller's flat buffer
     // (off_fnw / off_fnb, directly behind head.bias) and the frozen norm_w / norm_b are not used; DYT_CREATE_AVG_POOL (given with DYT_CREATE_FC_NORM only): the row

@@ -1,7 +1,7 @@
 // Wide classification head (DYT_CREATE_WIDE_HEAD): final LayerNorm of the cls rows + Linear(768, C) for C up to 65 536, forward
 // and backward, as exact-fp32 MFMA GEMMs (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, in every precision mode).
 //
-// The row kernels of rowops.hip (head_fwd / head_bwd_dx / head_bwd_dw) walk all C rows of head.weight once per image and stage a
+// The row kernels of step_tail.hip (head_fwd / head_bwd_dx / head_bwd_dw) walk all C rows of head.weight once per image and stage a
 // dlogits row in a 1024-float LDS array: right at C = 100 ... 1000, where the head is microseconds.  At C = 21 843 (the
 // ImageNet-21K classifier) and B = 128 the three products are 4.3 GFLOP GEMMs over a 67 MB matrix; here each reads it once per
 // 64 images:
@@ -21,8 +21,6 @@
 #include "head_wide_idx.h"
 
 namespace dyt {
-
-#define LAUNCH_CHECK() DYT_HIP_CHECK(hipGetLastError())
 
 using namespace hw;
 

@@ -1,7 +1,7 @@
 // Byte-image input: uint8 batches normalised where the patch embedding loads them (DYT_F_IMAGES_U8), and dyt_normalize_u8.
 //
 //   im2col_u8_kernel<AT, NHWC>   bytes [B,3,224,224] / [B,224,224,3] -> the EPI_EMBED GEMM's A operand, the buffer and element order of
-//                                im2col_kernel (rowops.hip): out[(b*196 + py*14 + px)*768 + c*256 + i*16 + j]
+//                                im2col_kernel (embed.hip): out[(b*196 + py*14 + px)*768 + c*256 + i*16 + j]
 //   normalize_u8_kernel<NHWC>    the same bytes -> fp32 [B,3,224,224]
 //
 // Both evaluate input_norm_value (input_norm.h) -- ((float)u / 255.0f - mean[c]) / std[c], three correctly rounded fp32 operations --

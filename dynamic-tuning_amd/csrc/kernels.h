@@ -166,9 +166,9 @@ void set_gemm_splitk(int on);   // DYT_OPT_GEMM_SPLITK
 int get_gemm_splitk();
 
 // ------------------------------------------------------------------------------------------
-// row-wise / small kernels
+// row-wise / small kernels (ln.hip, dispatch.hip, embed.hip, step_tail.hip, block_bwd.hip, wgrad.hip)
 // ------------------------------------------------------------------------------------------
-// LayerNorm over 768 channels, one wave per row; stats[row] = {mean, rstd}
+// ln.hip: LayerNorm over 768 channels, one wave per row; stats[row] = {mean, rstd}
 int launch_ln_fwd(int precision, const float* x, const float* w, const float* b, void* out, float2* stats,
                   int rows, hipStream_t s, void* out3 = nullptr, int out3_f8 = 0);   // out3 (fp32 mode): the rows as split 16-bit operand [rows, SPLIT_A*768] instead of out; out3_f8: in the hi16 / fp8 form (store4_split_f8)
 int launch_ln_fwd_f32out(const float* x, const float* w, const float* b, float* out, int rows, hipStream_t s);
@@ -185,6 +185,7 @@ int launch_adapter_ln_fwd(int out_at_precision, const float* x, const float* w, 
 int launch_ln_param_grad(int precision, const void* dy, const float* x, const float2* stats, float* partial, float* out, int rows, float gs, hipStream_t s);
 int64_t ln_param_grad_scratch_floats(int rows);
 
+// dispatch.hip: the token dispatcher
 struct GateArgs {
     const float* u;          // [B*197,768] residual stream after attention
     const float* w;          // [768]
@@ -222,6 +223,7 @@ int launch_ln_cls(int precision, const float* u, const float* w, const float* b,
                   int batch, hipStream_t s);
 int launch_cls_index(int* cls_rows, int batch, hipStream_t s);
 
+// embed.hip: patch-embedding prologue and the dtype / layout converters
 int launch_im2col(int precision, const float* images, void* out, int batch, hipStream_t s);
 // input_u8.hip: the same operand from a uint8 batch ([B,3,224,224], nhwc: [B,224,224,3]), normalised with nm in the load; and the plain fp32 image
 int launch_im2col_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, hipStream_t s);
@@ -237,7 +239,7 @@ int launch_transpose_convert(int precision, const float* src, void* dst, int row
 int launch_pad_convert(int precision, const float* src, void* dst, int rows, int cols, int dst_rows,
                        int dst_cols, hipStream_t s);
 
-// head: final LayerNorm on the cls rows + Linear(768, C)
+// step_tail.hip (to launch_adamw_segments below).  head: final LayerNorm on the cls rows + Linear(768, C)
 // (x row b at x + b * x_stride: the cls rows of the token stream by default, the [B,768] pooled rows under DYT_CREATE_AVG_POOL)
 int launch_head_fwd(const float* x, const float* nw, const float* nb, const float* hw, const float* hb,
                     float* cls_n, float2* stats, float* logits, int batch, int C, hipStream_t s, size_t x_stride = (size_t)NT * D);
@@ -300,7 +302,7 @@ struct AdamwSegTable { AdamwSeg s[128]; };
 int launch_adamw_segments(float* p, const float* g, float* m, float* v, int64_t n, int* state, const AdamwSegTable& table, int nseg,
                           float b1, float b2, float eps, float bc1, float rsqrt_bc2, float gscale, hipStream_t s);
 
-// backward prep for one block: g_at = AT(g) ; dH[dst_of[t]] = AT(g[t] * mask) ;
+// block_bwd.hip (to launch_scale_rows below).  backward prep for one block: g_at = AT(g) ; dH[dst_of[t]] = AT(g[t] * mask) ;
 // dmask[token] = <g[token], h[r]> for kept rows (0 elsewhere)
 struct BwdPrepArgs {
     const float* g;         // [M,768]
@@ -370,7 +372,7 @@ int launch_tok_bwd(int precision, const TokBwdArgs& a, int* nblocks_out, hipStre
 int launch_drop_path_draw(float* scales, int depth, int batch, float rate, uint64_t seed, const uint64_t* seed_dev, uint64_t subseq_base, hipStream_t s);
 // x[row, :] *= scale[row / 197] for an AT matrix [M, ld] (the attention branch's gradient after the proj dgrad)
 int launch_scale_rows(int precision, void* x, const float* scale, int M, int ld, hipStream_t s);
-// out[i] += alpha * sum_p partial[p*stride + i], i < n
+// wgrad.hip (to flush_reductions below).  out[i] += alpha * sum_p partial[p*stride + i], i < n
 int launch_reduce_partials(const float* partial, int nparts, int stride, float* out, int n, float alpha,
                            hipStream_t s);
 

@@ -14,8 +14,6 @@
 
 namespace dyt {
 
-#define LAUNCH_CHECK() DYT_HIP_CHECK(hipGetLastError())
-
 // ------------------------------------------------------------------------------------------
 // xf = LN_final(x) (fp32, kept: it is the input of norm_k / norm_v) ; xk = LN_k(xf) ; xv = LN_v(xf)
 // norm_k and norm_v see the same input, so they share (mean, rstd).

@@ -18,8 +18,6 @@
 
 namespace dyt {
 
-#define LAUNCH_CHECK() DYT_HIP_CHECK(hipGetLastError())
-
 namespace {
 constexpr int AP_WAVES = 7;                  // runs per output channel
 constexpr int AP_RUN = NP / AP_WAVES;        // 28 rows per run

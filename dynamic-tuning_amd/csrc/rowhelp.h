@@ -1,7 +1,9 @@
-// Wave-per-row helpers shared by the row-wise kernels (rowops.hip, pool.hip): one 64-lane wave owns one
-// 768-channel token row (3 x float4 per lane, fully coalesced); reductions are wave shuffles.
+// Wave-per-row helpers shared by the row-wise kernels (ln, dispatch, step_tail, block_bwd, wgrad, pool, pool_avg, head_wide .hip):
+// one 64-lane wave owns one 768-channel token row (3 x float4 per lane, fully coalesced); reductions are wave shuffles.
 #pragma once
 #include "dyt_common.h"
+
+#define LAUNCH_CHECK() DYT_HIP_CHECK(hipGetLastError())   // after the launches of a launcher: returns the error code from it
 
 namespace dyt {
 

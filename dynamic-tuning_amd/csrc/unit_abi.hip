@@ -509,7 +509,7 @@ extern "C" int dyt_gate_compact(const float* u, const float* w, const float* b, 
     return DYT_OK;
 }
 
-// ---- the backward row kernels alone (rowops.hip: bwd_prep, ln_bwd, ln_param_grad / ln_param_reduce, tok_bwd + the deferred gate-gradient
+// ---- the backward row kernels alone (block_bwd.hip, ln.hip: bwd_prep, ln_bwd, ln_param_grad / ln_param_reduce, tok_bwd + the deferred gate-gradient
 // ---- reduction): argument checks, the product's own launch_* function, synchronise.  Test-only (tests/test_gpu_row_bwd.py). ----
 static int unit_precision_ok(const char* who, int precision) {
     if (precision == 0 || precision == 1) return 0;

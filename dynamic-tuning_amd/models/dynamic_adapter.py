@@ -19,7 +19,7 @@ from _lib import DyTError, check, lib, ptr, stream_ptr
 def _gumbel_sigmoid(logits, tau=1, hard=False, eps=1e-10, training=True, threshold=0.5, gumbels=None):
     """Reference models/dynamic_adapter.py:25-54 (same signature; ``gumbels=(g1, g2)`` optionally
     injects the two Gumbel draws).  Element-wise utility kept for API parity; the model path
-    evaluates the same formula inside the gate kernel (csrc/rowops.hip: gate_kernel)."""
+    evaluates the same formula inside the gate kernel (csrc/dispatch.hip: gate_select_kernel)."""
     if training:
         if gumbels is None:
             g1 = -torch.empty_like(logits).exponential_().log()

@@ -1,6 +1,6 @@
 """``models.losses.AdaLoss`` of the reference (models/losses.py:15-84): same constructor signature, same attributes, same return
 value.  Host-side glue on the [B,C] logits and the [B,12,196,1] mask tensor the model returns (the module-API path); the fused step
-evaluates the same loss inside libdyt_hip (csrc/rowops.hip: loss_rows_kernel / loss_final_kernel)."""
+evaluates the same loss inside libdyt_hip (csrc/step_tail.hip: loss_rows_kernel / loss_final_kernel)."""
 import torch.nn as nn
 
 

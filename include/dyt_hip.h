@@ -499,7 +499,7 @@ int dyt_mlp_gathered_fwd(dyt_ctx* ctx, int layer, const float* u, const float* m
  * models/model_speed_test.py:297-305.  Unit-test entry: recomputes the forward, allocates scratch and synchronises. */
 int dyt_mlp_gathered_bwd(dyt_ctx* ctx, int layer, const float* u, const float* mask, const float* dy, float* du, int batch, void* stream);
 
-/* ---- the backward row kernels alone (csrc/rowops.hip), for tests/test_gpu_row_bwd.py.  Each entry checks its arguments (DYT_ERR_ARG with
+/* ---- the backward row kernels alone (csrc/block_bwd.hip, csrc/ln.hip), for tests/test_gpu_row_bwd.py.  Each entry checks its arguments (DYT_ERR_ARG with
  * a text, before anything is enqueued), launches the product's own kernel through the launcher csrc/backward.hip calls, and synchronises.
  * Added without an ABI version change (the version stays 5), discovered by their symbols like dyt_adamw_segments.
  * `precision` is DYT_PREC_FP32 or DYT_PREC_BF16; at 1 every `void*` operand is of the library's 16-bit type (bfloat16 in libdyt_hip.so,

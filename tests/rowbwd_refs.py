@@ -1,4 +1,4 @@
-"""Plain-torch CPU references of the row kernels that carry the gradient from one block to the next (csrc/rowops.hip: bwd_prep, ln_bwd,
+"""Plain-torch CPU references of the row kernels that carry the gradient from one block to the next (csrc/block_bwd.hip and csrc/ln.hip: bwd_prep, ln_bwd,
 ln_param_grad / ln_param_reduce, tok_bwd with the deferred gate-gradient reduction), for tests/test_gpu_row_bwd.py.
 
 As tests/tail_refs.py: every function takes ``dtype`` -- float64 is the reference, float32 gives the error floor of plain fp32 arithmetic

@@ -1,4 +1,4 @@
-"""Plain-torch CPU references of the kernels that finish a step (csrc/rowops.hip: loss_rows / loss_final, head_fwd / head_bwd_dw,
+"""Plain-torch CPU references of the kernels that finish a step (csrc/step_tail.hip: loss_rows / loss_final, head_fwd / head_bwd_dw,
 adamw / adamw_guarded / grad_nonfinite, sqsum / clip_scale), for tests/test_gpu_step_tail.py.
 
 Every function takes ``dtype``: float64 is the reference; the GPU tests evaluate the same function a second time in float32 to learn how

@@ -1,4 +1,4 @@
-"""Parameter groups of the fused AdamW on the GPU: dyt_adamw_segments (csrc/rowops.hip adamw_segments_kernel) on plain fp32 tensors through
+"""Parameter groups of the fused AdamW on the GPU: dyt_adamw_segments (csrc/step_tail.hip adamw_segments_kernel) on plain fp32 tensors through
 the C ABI, then inside the model behind torch.optim.AdamW(param_groups_lrd(...)).
 
 The kernel's contract is that every element sees the arithmetic of the one-group kernels, so the first yardstick is exact: one segmented

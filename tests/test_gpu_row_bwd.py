@@ -1,4 +1,4 @@
-"""Unit tests of the row kernels that carry the gradient from one block to the next (csrc/rowops.hip), each alone through its unit entry
+"""Unit tests of the row kernels that carry the gradient from one block to the next (csrc/block_bwd.hip, csrc/ln.hip), each alone through its unit entry
 (include/dyt_hip.h: dyt_unit_bwd_prep, dyt_unit_ln_bwd, dyt_unit_ln_param_grad, dyt_unit_tok_bwd) next to an fp64 reference
 (tests/rowbwd_refs.py, pinned to autograd by tests/test_rowbwd_refs_host.py):
 
@@ -34,7 +34,7 @@ of one run, not bounds):
                                                                 (fp16 stream form): 0.992 of what it is allowed (B=2 bf16)
   tok_bwd + reduce_partials_batch  d_gate                       1.03 (dad + du_at, B=2 bf16, d_gate[0:768])
 
-Each of these edits to csrc/rowops.hip turns the named tests red (checked once on the MI355X, on scratch copies): `dmk *= bs` dropped --
+Each of these edits to csrc/block_bwd.hip / csrc/ln.hip turns the named tests red (checked once on the MI355X, on scratch copies): `dmk *= bs` dropped --
 test_tok_bwd_branch_scale; the cat subtraction dropped -- test_tok_bwd_cat_correction; `du += e` without inv_gs --
 test_tok_bwd_16bit_adapter_dgrad_and_stream[fp16]; `/ a.tau` skipped, or rv read at lane (k >> 2) ^ 1 -- every tok_bwd test with a gate,
 resp. with dA2 (26 cases each); dmask_next from the gs-scaled row in ln_bwd_kernel -- test_ln_bwd[3 / 4 / 5 / 197-fp16].

@@ -1,4 +1,4 @@
-"""Unit tests of the kernels that finish a step (csrc/rowops.hip), each next to an fp64 reference (tests/tail_refs.py), through the C ABI:
+"""Unit tests of the kernels that finish a step (csrc/step_tail.hip), each next to an fp64 reference (tests/tail_refs.py), through the C ABI:
 
   loss_rows_kernel / loss_final_kernel          dyt_loss after one saved student pass has filled the slot's token counts
   head_fwd_kernel / head_bwd_dw_kernel          dyt_forward / dyt_backward: logits, d head.weight, d head.bias
