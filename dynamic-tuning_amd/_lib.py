@@ -215,6 +215,58 @@ def normalize_u8(images, mean, std, out=None):
     return out
 
 
+def _mix_params_ptr(params):
+    import torch
+    if not (torch.is_tensor(params) and params.is_cuda and params.dtype == torch.int32 and params.is_contiguous() and params.numel() == 16):
+        raise DyTError("mix parameters: a contiguous int32[16] device tensor (util.mixup.MixDraw.words())")
+    return ptr(params)
+
+
+def mix_images(images, params, frames=1, norm=None, out=None):
+    """dyt_mix_images: a device batch -- fp32 [n,3,224,224], uint8 [n,3,224,224] or uint8 [n,224,224,3] -- mixed with its mirrored batch as
+    the device block ``params`` (int32[16]: csrc/mix.h MixParams) says -> fp32 [n,3,224,224], on torch's current stream.  uint8 images are
+    normalised with ``norm`` = (mean, std) first.  n = clips * frames with an even number of clips."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_mix_images"):
+        raise DyTError("this libdyt_hip has no dyt_mix_images (on-device mixup): rebuild it")
+    layout = byte_image_layout(images)
+    if layout is None and not (images.dtype == torch.float32 and tuple(images.shape[1:]) == (3, 224, 224)):
+        raise DyTError("mix_images takes fp32 [n,3,224,224] or uint8 images (got %s %s)" % (images.dtype, tuple(images.shape)))
+    if layout is not None and norm is None:
+        raise DyTError("mix_images: uint8 images need norm=(mean, std) (the model's input_norm)")
+    n, frames = int(images.shape[0]), int(frames)
+    if frames < 1 or n % frames != 0 or (n // frames) % 2 != 0:
+        raise DyTError("mix: an odd number of images / clips cannot be paired (%d images, %d frame(s) per clip)" % (n, frames))
+    images = images.contiguous()
+    if out is None:
+        out = torch.empty(n, 3, 224, 224, device=images.device, dtype=torch.float32)
+    kind = 0 if layout is None else (2 if layout == "nhwc" else 1)
+    mean, std = (float3(norm[0]), float3(norm[1])) if layout is not None else (None, None)
+    with torch.cuda.device(images.device):
+        check(L.dyt_mix_images(ptr(images), ptr(out), n, frames, kind, mean, std, _mix_params_ptr(params), stream_ptr()), L)
+    return out
+
+
+def mix_targets(labels, num_classes, params, out=None):
+    """dyt_mix_targets: integer labels [rows] (device) -> the class-probability rows fp32 [rows, num_classes] of the draw in ``params``."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_mix_targets"):
+        raise DyTError("this libdyt_hip has no dyt_mix_targets (on-device mixup): rebuild it")
+    if labels.dim() != 1 or labels.is_floating_point():
+        raise DyTError("mix_targets takes integer labels [rows] (got %s %s)" % (labels.dtype, tuple(labels.shape)))
+    rows = int(labels.shape[0])
+    if rows % 2 != 0:
+        raise DyTError("mix: an odd number of images / clips cannot be paired (%d rows)" % rows)
+    labels = labels.long().contiguous()
+    if out is None:
+        out = torch.empty(rows, int(num_classes), device=labels.device, dtype=torch.float32)
+    with torch.cuda.device(labels.device):
+        check(L.dyt_mix_targets(ptr(labels), ptr(out), rows, int(num_classes), _mix_params_ptr(params), stream_ptr()), L)
+    return out
+
+
 _lib = None
 
 _vp, _i, _i64, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
@@ -244,6 +296,9 @@ SYMBOLS = {
     "dyt_set_soft_targets": (_i, [_vp, _vp, _i]),
     "dyt_set_input_norm": (_i, [_vp, ctypes.POINTER(_f), ctypes.POINTER(_f)]),
     "dyt_normalize_u8": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp]),
+    "dyt_set_mix": (_i, [_vp, _vp, _i]),
+    "dyt_mix_images": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _vp]),
+    "dyt_mix_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
     "dyt_trainable_numel": (_i, [_vp, ctypes.POINTER(_i64)]),
     "dyt_trainable_offset": (_i, [_vp, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
@@ -293,7 +348,7 @@ SYMBOLS = {
 
 # Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
-OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8",
+OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
                     "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
 
 _lib16 = None

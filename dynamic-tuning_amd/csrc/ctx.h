@@ -160,6 +160,9 @@ struct dyt_ctx {
     int split_bwd_parts = 3;    // ... products of the GRADIENT GEMMs' contraction (3 full, 1 = dY_hi * W_hi: "fp16x3f")
     int split_bwd_attn_parts = 3;   // ... and of the split attention backward's dP / dQ / dK / dV products (3 or 1; the score recomputation keeps three)
     const float* soft_targets = nullptr; int soft_batch = 0;   // dyt_set_soft_targets: class-probability targets of the next loss evaluations
+    // dyt_set_mix: while mix_params (a DEVICE block the kernels read at run time) is set, forward_impl launches the mixing im2col and
+    // dyt_step_fwd_bwd writes the class-probability rows into mix_soft ([max_batch][num_classes], allocated by the first dyt_set_mix) for its loss
+    const MixParams* mix_params = nullptr; int mix_frames = 1; float* mix_soft = nullptr; size_t mix_soft_bytes = 0;
     bool split16 = false;       // fp32 mode: frozen-weight GEMMs as three 16-bit MFMA products (DYT_OPT_F32_SPLIT16)
     void* pe_w3 = nullptr;
     // 16-bit modes: LayerNorm-2 is not a kernel -- the proj epilogue emits per-row partial statistics of u, fc1 contracts the 16-bit copy
@@ -225,6 +228,8 @@ namespace dyt {
 int refuse_inference(const dyt_ctx* c, const char* what);
 int set_matrix(dyt_ctx* c, const float* src, void* w, void* wT, int N, int K, hipStream_t s);
 hipEvent_t get_event(dyt_ctx* c);
+// mix.hip
+int check_mix_batch(const dyt_ctx* c, int batch);   // mix on: an image count that cannot be paired, DYT_ERR_ARG with a text
 // forward.hip
 int prep_adapters(dyt_ctx* c, const float* trainable, hipStream_t s);
 int prep_pool(dyt_ctx* c, const float* tr, hipStream_t s);

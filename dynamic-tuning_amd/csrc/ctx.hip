@@ -438,13 +438,14 @@ extern "C" int dyt_ctx_destroy(dyt_ctx* c) {
     if (c->side) hipStreamDestroy(c->side);
     if (c->arena) hipFree(c->arena);
     if (c->aux_arena) hipFree(c->aux_arena);
+    if (c->mix_soft) hipFree(c->mix_soft);
     delete c;
     return DYT_OK;
 }
 
 extern "C" int dyt_ctx_bytes(const dyt_ctx* c, int64_t* bytes) {
     if (!c || !bytes) { set_error("null argument"); return DYT_ERR_ARG; }
-    *bytes = (int64_t)(c->arena_size + c->aux_size);
+    *bytes = (int64_t)(c->arena_size + c->aux_size + c->mix_soft_bytes);
     return DYT_OK;
 }
 
@@ -730,6 +731,7 @@ extern "C" int dyt_set_soft_targets(dyt_ctx* c, const float* targets, int rows) 
     if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
     if (targets && rows < 1) { set_error("soft targets: rows = %d", rows); return DYT_ERR_ARG; }
     if (targets) { int rc = refuse_inference(c, "dyt_set_soft_targets"); if (rc) return rc; }
+    if (targets && c->mix_params) { set_error("dyt_set_soft_targets: mix is on (dyt_set_mix) and writes the class-probability targets itself"); return DYT_ERR_STATE; }
     c->soft_targets = targets; c->soft_batch = targets ? rows : 0;
     return DYT_OK;
 }

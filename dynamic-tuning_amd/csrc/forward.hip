@@ -170,6 +170,8 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     if (!images || !trainable || !logits) { set_error("null argument"); return DYT_ERR_ARG; }
     if ((g1 == nullptr) != (g2 == nullptr)) { set_error("g1 and g2 must be given together"); return DYT_ERR_ARG; }
     { int rc = check_image_input(flags, images); if (rc) return rc; }   // DYT_F_IMAGES_U8 / _NHWC: `images` is a byte batch
+    const bool mix = c->mix_params && !(flags & DYT_F_TOKENS_IN);   // dyt_set_mix: the embedding load mixes every image with its partner
+    if (mix) { int rc = check_mix_batch(c, B); if (rc) return rc; }
     if (flags & DYT_F_SAVE) { int rc = refuse_inference(c, slot > 0 ? "dyt_forward with DYT_F_SAVE into a slot > 0" : "dyt_forward with DYT_F_SAVE"); if (rc) return rc; }
     if ((flags & DYT_F_TRAINING) && c->drop_path_rate > 0.f) { int rc = refuse_inference(c, "a training forward with stochastic depth"); if (rc) return rc; }
     const int P = c->prec, depth = c->cfg.depth, M = B * NT, r = c->cfg.ffn_num;
@@ -213,7 +215,11 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
         DYT_HIP_CHECK(hipMemcpyAsync(S.xs[0], images, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else if (!share0) {
         // patch embedding: im2col + GEMM (+bias +pos_embed), cls rows
-        if (flags & DYT_F_IMAGES_U8)   // bytes, normalised in the load: the same operand bits as the float path on the normalised image
+        if (mix && (flags & DYT_F_IMAGES_U8))
+            RUN(2, 0, launch_im2col_mix_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, c->mix_frames, c->mix_params, s));
+        else if (mix)
+            RUN(2, 0, launch_im2col_mix(P, images, T.xn, B, c->mix_frames, c->mix_params, s));
+        else if (flags & DYT_F_IMAGES_U8)   // bytes, normalised in the load: the same operand bits as the float path on the normalised image
             RUN(2, 0, launch_im2col_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, s));
         else
             RUN(2, 0, launch_im2col(P, images, T.xn, B, s));

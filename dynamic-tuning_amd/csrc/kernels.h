@@ -4,6 +4,7 @@
 #include "dyt_common.h"
 #include "attn_route.h"
 #include "input_norm.h"
+#include "mix.h"
 
 namespace dyt {
 
@@ -228,6 +229,12 @@ int launch_im2col(int precision, const float* images, void* out, int batch, hipS
 // input_u8.hip: the same operand from a uint8 batch ([B,3,224,224], nhwc: [B,224,224,3]), normalised with nm in the load; and the plain fp32 image
 int launch_im2col_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, hipStream_t s);
 int launch_normalize_u8(const uint8_t* src, float* dst, int batch, int nhwc, const InputNorm& nm, hipStream_t s);
+// mix.hip: the same loads with Mixup / CutMix applied (parameters in device memory), fp32 images out, class-probability rows
+int launch_im2col_mix(int precision, const float* images, void* out, int batch, int frames, const MixParams* params, hipStream_t s);
+int launch_im2col_mix_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, int frames,
+                         const MixParams* params, hipStream_t s);
+int launch_mix_images(const void* src, float* dst, int count, int frames, int src_kind, const InputNorm& nm, const MixParams* params, hipStream_t s);
+int launch_mix_targets(const int64_t* labels, float* out, int rows, int num_classes, const MixParams* params, hipStream_t s);
 int check_image_input(int flags, const void* images);   // DYT_F_IMAGES_U8 / _NHWC of a pass: flag combination and pointer alignment, DYT_ERR_ARG with a text
 int launch_cls_rows(const float* cls, const float* pos, float* x0, int batch, hipStream_t s);
 // fp32 -> AT copy (n elements)

@@ -1,10 +1,12 @@
 // Loss, AdamW and the fused step with its two-stream schedule; gradient hand-over, all-reduce and clipping.
 #include "ctx.h"
 
-extern "C" int dyt_loss(dyt_ctx* c, int slot_student, const float* logits_s, const float* logits_t, const int64_t* targets,
-                        int batch, float token_target_ratio, float token_loss_ratio, float token_minimal,
-                        float token_minimal_weight, float* dlogits_s, float* dlogits_t, float* out_losses, float* dtok,
-                        void* stream) {
+// dyt_loss; mix_rows (dyt_step_fwd_bwd with mix on): the class-probability rows mix_targets_kernel wrote on this stream, read instead of
+// the caller-set soft targets or the labels
+static int loss_impl(dyt_ctx* c, int slot_student, const float* logits_s, const float* logits_t, const int64_t* targets,
+                     int batch, float token_target_ratio, float token_loss_ratio, float token_minimal,
+                     float token_minimal_weight, float* dlogits_s, float* dlogits_t, float* out_losses, float* dtok,
+                     void* stream, const float* mix_rows) {
     if (!c || !logits_s || !logits_t || !targets || !dlogits_s || !dlogits_t || !out_losses || !dtok) {
         set_error("null argument");
         return DYT_ERR_ARG;
@@ -20,11 +22,21 @@ extern "C" int dyt_loss(dyt_ctx* c, int slot_student, const float* logits_s, con
     a.dlogits_s = dlogits_s; a.dlogits_t = dlogits_t; a.out_losses = out_losses; a.dtok = dtok;
     a.scratch = c->loss_part;
     if (batch * c->frames > c->cfg.max_batch) { set_error("batch %d exceeds max_batch", batch); return DYT_ERR_ARG; }
-    if (c->soft_targets) {
+    if (mix_rows) {
+        a.soft = mix_rows;
+    } else if (c->soft_targets) {
         if (c->soft_batch != batch) { set_error("soft targets were set for %d rows, this loss has %d", c->soft_batch, batch); return DYT_ERR_STATE; }
         a.soft = c->soft_targets;
     }
     return launch_loss(a, s);
+}
+
+extern "C" int dyt_loss(dyt_ctx* c, int slot_student, const float* logits_s, const float* logits_t, const int64_t* targets,
+                        int batch, float token_target_ratio, float token_loss_ratio, float token_minimal,
+                        float token_minimal_weight, float* dlogits_s, float* dlogits_t, float* out_losses, float* dtok,
+                        void* stream) {
+    return loss_impl(c, slot_student, logits_s, logits_t, targets, batch, token_target_ratio, token_loss_ratio, token_minimal,
+                     token_minimal_weight, dlogits_s, dlogits_t, out_losses, dtok, stream, nullptr);
 }
 
 extern "C" int dyt_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, int step,
@@ -97,6 +109,10 @@ extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* 
     if (!images || !targets || !grad_flat || !out_losses) { set_error("null argument"); return DYT_ERR_ARG; }
     { int rc = check_image_input(flags, images); if (rc) return rc; }   // byte images: refused here, before the step enqueues anything
     if (c->cfg.slots < 2) { set_error("dyt_step_fwd_bwd needs 2 slots"); return DYT_ERR_STATE; }
+    if (c->mix_params) {   // dyt_set_mix: refused here, before the step enqueues anything
+        if (c->soft_targets) { set_error("dyt_step_fwd_bwd: mix is on (dyt_set_mix) and class-probability targets are set (dyt_set_soft_targets)"); return DYT_ERR_STATE; }
+        int rc = check_mix_batch(c, batch); if (rc) return rc;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int depth = c->cfg.depth;
     const size_t nz = (size_t)depth * batch * NP;        // per-pass noise stride
@@ -163,8 +179,12 @@ extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* 
                       share ? &c->slots[0] : nullptr, nullptr, (share && par) ? c->ev_b0 : nullptr);
     if (rc) return rc;
     if (par) { DYT_HIP_CHECK(hipEventRecord(c->ev_join, s2)); DYT_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0)); }
-    rc = dyt_loss(c, 0, ls, lt, targets, batch / c->frames, token_target_ratio, token_loss_ratio, token_minimal, token_minimal_weight,
-                  c->dl_s, c->dl_t, out_losses, c->dtok, stream);
+    if (c->mix_params) {   // the class-probability rows of this draw, from the integer labels, on the step's stream ahead of the loss
+        rc = launch_mix_targets(targets, c->mix_soft, batch / c->frames, c->cfg.num_classes, c->mix_params, s);
+        if (rc) return rc;
+    }
+    rc = loss_impl(c, 0, ls, lt, targets, batch / c->frames, token_target_ratio, token_loss_ratio, token_minimal, token_minimal_weight,
+                   c->dl_s, c->dl_t, out_losses, c->dtok, stream, c->mix_params ? c->mix_soft : nullptr);
     if (rc) return rc;
     float* gt = par ? c->grad2 : grad_flat;  // teacher-pass gradients
     // measurement hook: DYT_DBG_TEACHER_NAN=1 feeds the teacher's backward pass NaN (every value it computes or stores is NaN) and

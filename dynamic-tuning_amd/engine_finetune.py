@@ -17,6 +17,7 @@ import torch.distributed as dist
 
 import util.lr_sched as lr_sched
 from _lib import DyTError
+from util.mixup import DeviceMixup
 from util.metrics import accuracy, mean_per_class_accuracy
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
@@ -510,12 +511,15 @@ def step_seed(epoch, it, base=None):
 
 def train_step(model, samples, targets, optimizer, criterion=None, losses_out=None, gumbel=None, keep_mask=None,
                seed=0, target_ratio=None, token_minimal=None, token_minimal_weight=None, accumulate=False, update=True,
-               accum_iter=1, max_norm=0.0, graph=False):
+               accum_iter=1, max_norm=0.0, graph=False, mix=None):
     """One fused step (reference engine_finetune.py:47-79) on device tensors; returns the device
     tensor of loss components [loss, base, token, teacher, distillation, keep ratio, kept, 0].
     graph=True replays the forward+backward from a captured hipGraph (on-device noise only).
     ``targets``: integer labels [b], or class probabilities [b, num_classes] (a ``mixup_fn``'s output, reference :44-45) -- both
-    CrossEntropyLoss terms then take the soft form (C ABI dyt_set_soft_targets)."""
+    CrossEntropyLoss terms then take the soft form (C ABI dyt_set_soft_targets).
+    ``mix``: a util.mixup.MixDraw (``DeviceMixup.draw()``) -- ``samples`` is the UNMIXED batch (bytes stay bytes) and ``targets`` its integer
+    labels; the library mixes inside the patch-embedding load and writes the class-probability targets itself (C ABI dyt_set_mix), the
+    criterion's own label_smoothing on top.  graph=True stays honoured: the draw is device data of the captured step."""
     m = getattr(model, "module", model)
     if getattr(m, "inference_only", False):
         raise DyTError("train_step: the model was built with inference_only (eval forwards only); build it without inference_only to train")
@@ -523,7 +527,17 @@ def train_step(model, samples, targets, optimizer, criterion=None, losses_out=No
     eng = m.engine(samples.shape[0], samples.device)
     # nn.CrossEntropyLoss(label_smoothing = e) is the soft form with t (1 - e) + e / C (torch applies the same map to class-probability targets)
     smooth = float(getattr(getattr(criterion, "base_criterion", None), "label_smoothing", 0.0) or 0.0)
-    if smooth > 0.0 and not (targets.dim() == 2 and targets.is_floating_point()):
+    if mix is not None:
+        if targets.dim() != 1 or targets.is_floating_point():
+            raise DyTError("train_step(mix=...) takes the integer labels of the unmixed batch (got %s %s)" % (targets.dtype, tuple(targets.shape)))
+        if (samples.shape[0] // eng.frames) % 2 != 0:   # timm refuses an odd batch too; here before anything is enqueued
+            raise DyTError("mix: an odd number of images / clips cannot be paired (batch %d, %d frame(s) per clip)" % (samples.shape[0], eng.frames))
+        eng.set_soft_targets(None)
+        eng.set_mix(mix, smooth)   # the labels go to the step as they are: the library forms the smoothed, mixed rows from them
+        targets = targets.long()
+    else:
+        eng.set_mix(None)
+    if mix is None and smooth > 0.0 and not (targets.dim() == 2 and targets.is_floating_point()):
         targets = torch.nn.functional.one_hot(targets.long(), eng.num_classes).float()
     if targets.dim() == 2 and targets.is_floating_point():
         soft = targets.float().contiguous()
@@ -708,13 +722,16 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         keep_mask = extra[1].to(device).contiguous() if len(extra) > 1 and extra[1] is not None else None
         if it % accum_iter == 0:   # per-iteration schedule, reference :43-46
             lr = lr_sched.adjust_learning_rate(optimizer, it / nsteps + epoch, args)
-        if mixup_fn is not None:   # reference :44-45 (timm.data.Mixup or any callable of that shape): mixed samples, class-probability targets
+        mix = None
+        if isinstance(mixup_fn, DeviceMixup):   # the mix happens inside the fused step: the batch stays as it is (bytes stay bytes), labels stay integers
+            mix = mixup_fn.draw()
+        elif mixup_fn is not None:   # reference :44-45 (timm.data.Mixup or any callable of that shape): mixed samples, class-probability targets
             if m.takes_bytes(samples):   # timm's Mixup multiplies in place: it gets the fp32 images the byte path would compute with (dyt_normalize_u8)
                 samples = m.bytes_to_float(samples)
             samples, targets = mixup_fn(samples, targets)
         train_step(model, samples, targets, optimizer, criterion, losses_out=step_losses, seed=step_seed(epoch, it),
                    gumbel=gumbel, keep_mask=keep_mask, accumulate=(it % accum_iter != 0), update=((it + 1) % accum_iter == 0),
-                   accum_iter=accum_iter, max_norm=max_norm or 0.0, graph=use_graph)
+                   accum_iter=accum_iter, max_norm=max_norm or 0.0, graph=use_graph, mix=mix)
         acc += step_losses
         pending += 1
         if (it + 1) % print_freq == 0 or it + 1 == nsteps:
@@ -739,7 +756,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     stats = {k: v / max(count, 1) for k, v in sums.items()}
     stats["lr"] = lr
     if mixup_fn is not None and getattr(m, "_engine", None) is not None:
-        m._engine.set_soft_targets(None)   # evaluation / the next caller's steps use their integer labels
+        m._engine.set_mix(None)            # evaluation / the next caller's passes see their images unmixed ...
+        m._engine.set_soft_targets(None)   # ... and use their integer labels
     optimizer.publish_torch_state()   # an adopted torch.optim.AdamW now reports this epoch's moments / step count (misc.save_model)
     if is_dist_avail_and_initialized():  # metric_logger.synchronize_between_processes(), reference :104
         t = torch.tensor([stats[k] for k in LOSS_KEYS], device=device, dtype=torch.float64)

@@ -108,6 +108,7 @@ class DyTEngine:
         # power of two the gradient carries wherever the library holds it in 16 bits (IEEE-half builds: 2^12, dyt_ctx::gs); None: no scaling
         self.grad_scale_log2 = 12 if self.precision in (PREC_FP16, PREC_FP16X3H, PREC_FP16F8, PREC_FP16X3Q) else None
         self.input_norm = INPUT_NORMS["imagenet"]   # what the context normalises uint8 images with (set_input_norm); the library's default
+        self._mix_on, self._mix_dev = False, None   # set_mix: the context mixes in the embedding load; the static device block of the draws
 
     def _ck(self, rc):
         check(rc, self.L)
@@ -291,7 +292,8 @@ class DyTEngine:
         # (a float batch and a byte batch of one shape are two graphs, so are the two byte layouts -- their shapes differ -- and a byte
         # step is captured with the input norm of its time)
         key = (tuple(images.shape), images.dtype, self.input_norm if images.dtype == torch.uint8 else None, tuple(targets.shape),
-               float(target_ratio), float(loss_ratio), float(token_minimal), float(token_minimal_weight), bool(masked_dense), bool(accumulate))
+               float(target_ratio), float(loss_ratio), float(token_minimal), float(token_minimal_weight), bool(masked_dense), bool(accumulate),
+               bool(self._mix_on))   # mix on / off are two graphs (other kernels); the draw itself is device data, not part of the key
         ent = self._graphs.get(key)
         cur = torch.cuda.current_stream(self.device)
         if ent is None:
@@ -560,9 +562,62 @@ class DyTEngine:
                 raise DyTError("soft targets: a contiguous fp32 [rows, %d] tensor on the HIP device" % self.num_classes)
         if targets is None and getattr(self, "_soft_keep", None) is None:
             return
+        self._ck(self.L.dyt_set_soft_targets(self.h, ptr(targets), 0 if targets is None else int(targets.shape[0])))   # (refused while mix is on)
         self._soft_keep = targets
         self._graphs = {}
-        self._ck(self.L.dyt_set_soft_targets(self.h, ptr(targets), 0 if targets is None else int(targets.shape[0])))
+
+    # ---- on-device mixup / cutmix --------------------------------------------------------------
+    MIX_RING = 8   # pinned host slots the draws travel through
+
+    def set_mix(self, draw, criterion_smoothing=0.0):
+        """dyt_set_mix.  ``draw`` (util.mixup.MixDraw with its target fields filled, e.g. ``DeviceMixup.draw()``): the passes enqueued from now on
+        mix every image with its partner inside the patch-embedding load, and the fused step computes its loss against the draw's
+        class-probability rows (then mapped by the criterion's own ``label_smoothing``) from the INTEGER labels it is given.  None: off.
+        The engine keeps ONE static device block; a draw is written into a slot of a small pinned host ring and copied to the block with
+        a non-blocking copy on the current stream -- no synchronisation, and for a captured step the copy sits outside the graph, in
+        front of the replay (like seed_device): one graph serves every draw."""
+        if draw is None:
+            if self._mix_on:
+                self._ck(self.L.dyt_set_mix(self.h, None, self.frames))
+                self._mix_on = False
+            return
+        self._refuse_inference("set_mix")
+        if not hasattr(self.L, "dyt_set_mix"):
+            raise DyTError("this libdyt_hip has no dyt_set_mix (on-device mixup): rebuild it")
+        if draw.num_classes != self.num_classes:
+            raise DyTError("mix: the draw's targets have %r classes, the engine %d" % (draw.num_classes, self.num_classes))
+        words = draw.words(criterion_smoothing)
+        if self._mix_dev is None:
+            self._mix_dev = torch.zeros(16, dtype=torch.int32, device=self.device)
+            self._mix_ring = torch.zeros(self.MIX_RING, 16, dtype=torch.int32).pin_memory()
+            self._mix_events = [None] * self.MIX_RING
+            self._mix_at = 0
+        k = self._mix_at
+        self._mix_at = (k + 1) % self.MIX_RING
+        if self._mix_events[k] is not None:
+            self._mix_events[k].synchronize()   # the copy that read this slot MIX_RING draws ago: long complete, this does not wait
+        self._mix_ring[k].copy_(torch.frombuffer(bytearray(words), dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            self._mix_dev.copy_(self._mix_ring[k], non_blocking=True)
+            if self._mix_events[k] is None:
+                self._mix_events[k] = torch.cuda.Event()
+            self._mix_events[k].record()
+            if not self._mix_on:
+                self._ck(self.L.dyt_set_mix(self.h, ptr(self._mix_dev), self.frames))
+                self._mix_on = True
+
+    def mix_images(self, images, draw):
+        """The images the fused path computes with, as a plain fp32 batch [n,3,224,224] (dyt_mix_images with this engine's frames and
+        input norm): the reference point of ``set_mix``."""
+        from _lib import mix_images
+        params = torch.frombuffer(bytearray(draw.words()), dtype=torch.int32).to(self.device)
+        return mix_images(images, params, frames=self.frames, norm=self.input_norm)
+
+    def mix_targets(self, labels, draw, criterion_smoothing=0.0):
+        """The class-probability rows [rows, num_classes] the fused step's loss reads for ``draw`` (dyt_mix_targets)."""
+        from _lib import mix_targets
+        params = torch.frombuffer(bytearray(draw.words(criterion_smoothing)), dtype=torch.int32).to(self.device)
+        return mix_targets(labels, self.num_classes, params)
 
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on):

@@ -382,6 +382,32 @@ int dyt_loss(dyt_ctx* ctx, int slot_student, const float* logits_s, const float*
  * which are then ignored: CE = -sum_c t_c log p_c, d logits = p sum_c t_c - t.  NULL restores the integer labels. */
 int dyt_set_soft_targets(dyt_ctx* ctx, const float* targets, int rows);
 
+/* On-device Mixup / CutMix (timm's Mixup, mode='batch', restated in csrc/mix.h), fused into the patch-embedding load.  Added without an ABI
+ * version change (the version stays 5) and without a flag: the three entries are discovered by their symbols, and "mix on" is context state
+ * like the soft targets.
+ * The draw lives in DEVICE memory: params_dev points to 16 words, 16-byte aligned, laid out as csrc/mix.h's MixParams --
+ *   int32 mode (0 identity, 1 mixup, 2 cutmix); float lam, 1 - lam; int32 yl, yh, xl, xh (cutmix: rows [yl,yh) x columns [xl,xh) come from
+ *   the partner); float on, off (target row: off everywhere, on at the label); int32 smooth_on, float keep, add (the criterion's own label
+ *   smoothing on top: t * keep + add); 4 reserved words
+ * -- and is read by the kernels when they RUN, never copied into their arguments: a captured step replayed after the block was overwritten
+ * mixes with the new draw.  Image n of a batch pairs with image count-1-n (video: the same frame of the mirrored clip).
+ * dyt_set_mix: while params_dev is set, every pass of this context that takes images (dyt_forward, dyt_step_fwd_bwd; uint8 or fp32) mixes
+ * them where the embedding operand is produced -- bit for bit the float path on dyt_mix_images' output -- and dyt_step_fwd_bwd computes its
+ * loss against the class-probability rows dyt_mix_targets would write from its integer labels (context-owned buffer of max_batch x
+ * num_classes floats, allocated by the first call: make that call outside a stream capture).  The pointer is kept, not copied; NULL turns
+ * mix off, and the passes launch exactly the kernels they launched before.  `frames` must be the context's.  Refused with a text, before
+ * anything is enqueued: an inference_only context, an odd number of images / clips (by the pass), mix together with dyt_set_soft_targets
+ * (DYT_ERR_STATE). */
+int dyt_set_mix(dyt_ctx* ctx, const void* params_dev, int frames);
+/* The mixed images as a plain fp32 batch, without a context: src fp32 [count,3,224,224] (src_kind 0), uint8 [count,3,224,224] (1) or uint8
+ * [count,224,224,3] (2) -> dst fp32 [count,3,224,224]; bytes are normalised with mean / std (host arrays, as dyt_normalize_u8; unused and
+ * may be NULL for src_kind 0) before they are mixed.  count = clips * frames, an even number of clips.  One launch on `stream`. */
+int dyt_mix_images(const void* src, float* dst, int count, int frames, int src_kind, const float mean[3], const float std[3], const void* params_dev, void* stream);
+/* The class-probability rows of a draw: labels int64 [rows] -> out fp32 [rows, num_classes] (16-byte aligned),
+ * out[r] = lam t(labels[r]) + (1 - lam) t(labels[rows-1-r]), three fp32 roundings, then the criterion's smoothing if the block asks for it.
+ * rows even, 1 <= num_classes <= 65 536.  One launch on `stream`. */
+int dyt_mix_targets(const int64_t* labels, float* out, int rows, int num_classes, const void* params_dev, void* stream);
+
 /* torch.optim.AdamW over the flat trainable buffer -- main_image.py:285; the gradient is first
  * multiplied by grad_scale (1/world_size after a SUM all-reduce).  `step` is 1-based. */
 int dyt_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
