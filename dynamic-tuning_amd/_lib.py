@@ -267,6 +267,60 @@ def mix_targets(labels, num_classes, params, out=None):
     return out
 
 
+# csrc/eval_stats.h / DYT_EVAL_* of include/dyt_hip.h: the int64 `counts` state of the streaming evaluation
+EVAL_HEAD_WORDS, EVAL_ROWS, EVAL_IGNORED, EVAL_NAN_ROWS, EVAL_MASK_ROWS = 8, 0, 1, 2, 3
+EVAL_RANK_BINS, EVAL_OFF_RANK, EVAL_OFF_KEEP = 16, 8, 24
+
+
+def eval_counts_words(layers, tokens):
+    return EVAL_OFF_KEEP + int(layers) * (int(tokens) + 1)
+
+
+def eval_rows(logits, labels, counts, per_class, loss_sum, row_rank, row_loss):
+    """dyt_eval_rows: fp32 logits [rows, C] (any row stride, unit inner stride) and int64 labels [rows] are folded into the device state
+    (``counts`` int64, ``per_class`` int64 [2 C] or None, ``loss_sum`` float64 [1]; all accumulate); ``row_rank`` int32 / ``row_loss`` fp32
+    (at least ``rows`` elements) receive the per-row results.  Two launches on torch's current stream, no host synchronisation."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_eval_rows"):
+        raise DyTError("this libdyt_hip has no dyt_eval_rows (streaming evaluation): rebuild it")
+    if not (torch.is_tensor(logits) and logits.is_cuda and labels.is_cuda):
+        raise DyTError("eval_rows takes device tensors (there is no CPU path)")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise DyTError("eval_rows takes fp32 logits [rows, classes] with unit inner stride (got %s %s, strides %s)" % (
+            logits.dtype, tuple(logits.shape), tuple(logits.stride())))
+    rows, classes = int(logits.shape[0]), int(logits.shape[1])
+    if labels.dim() != 1 or labels.is_floating_point() or labels.shape[0] != rows:
+        raise DyTError("eval_rows takes integer labels [%d] (got %s %s)" % (rows, labels.dtype, tuple(labels.shape)))
+    labels = labels.long().contiguous()
+    ld = int(logits.stride(0)) if rows > 1 else max(classes, int(logits.stride(0)))
+    if row_rank.numel() < rows or row_loss.numel() < rows:
+        raise DyTError("eval_rows: row_rank / row_loss hold fewer than %d elements" % rows)
+    if per_class is not None and per_class.numel() != 2 * classes:
+        raise DyTError("eval_rows: per_class holds %d words, 2 x %d classes expected" % (per_class.numel(), classes))
+    with torch.cuda.device(logits.device):
+        check(L.dyt_eval_rows(ctypes.c_void_p(logits.data_ptr()), ld, ptr(labels), rows, classes, ptr(counts), ptr(per_class), ptr(loss_sum),
+                              ptr(row_rank), ptr(row_loss), stream_ptr()), L)
+
+
+def eval_keep(token_select, counts, layers, tokens):
+    """dyt_eval_keep: fp32 masks [n, layers, tokens] (or [n, layers, tokens, 1]) -> the keep histogram of ``counts``; one launch."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_eval_keep"):
+        raise DyTError("this libdyt_hip has no dyt_eval_keep (streaming evaluation): rebuild it")
+    if not (torch.is_tensor(token_select) and token_select.is_cuda):
+        raise DyTError("eval_keep takes device tensors (there is no CPU path)")
+    if token_select.dim() == 4 and token_select.shape[-1] == 1:
+        token_select = token_select[..., 0]
+    if token_select.dim() != 3 or token_select.dtype != torch.float32 or tuple(token_select.shape[1:]) != (int(layers), int(tokens)):
+        raise DyTError("eval_keep takes fp32 masks [n, %d, %d] or [n, %d, %d, 1] (got %s %s)" % (
+            layers, tokens, layers, tokens, token_select.dtype, tuple(token_select.shape)))
+    token_select = token_select.contiguous()
+    with torch.cuda.device(token_select.device):
+        check(L.dyt_eval_keep(ptr(token_select), int(token_select.shape[0]), int(layers), int(tokens), ptr(counts), stream_ptr()), L)
+
+
 _lib = None
 
 _vp, _i, _i64, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
@@ -299,6 +353,8 @@ SYMBOLS = {
     "dyt_set_mix": (_i, [_vp, _vp, _i]),
     "dyt_mix_images": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _vp]),
     "dyt_mix_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "dyt_eval_rows": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dyt_eval_keep": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
     "dyt_trainable_numel": (_i, [_vp, ctypes.POINTER(_i64)]),
     "dyt_trainable_offset": (_i, [_vp, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
@@ -349,7 +405,7 @@ SYMBOLS = {
 # Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
-                    "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
+                    "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
 
 _lib16 = None
 

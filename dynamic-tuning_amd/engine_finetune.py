@@ -18,7 +18,7 @@ import torch.distributed as dist
 import util.lr_sched as lr_sched
 from _lib import DyTError
 from util.mixup import DeviceMixup
-from util.metrics import accuracy, mean_per_class_accuracy
+from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
 
@@ -792,10 +792,57 @@ def all_gather_concat(tensor):
     return torch.cat([o[:s] for o, s in zip(out, sizes)], dim=0)
 
 
+def stream_eval_requested(args=None):
+    """``args.stream_eval``, else the environment's DYT_STREAM_EVAL (for the reference's unchanged drivers behind dyt_run.py)."""
+    if getattr(args, "stream_eval", False):
+        return True
+    return os.environ.get("DYT_STREAM_EVAL", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+@torch.no_grad()
+def _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_dict, args, video):
+    """The streaming form of ``evaluate`` / ``evaluate_video``: every batch's logits, labels and token masks go straight into a
+    util.metrics.StreamingEval (three HIP launches, no host synchronisation); nothing is appended, concatenated or gathered, the ranks
+    merge with one SUM all-reduce of the state, and the state is read once.  Returns the gather form's keys plus ``acc1`` / ``acc5`` /
+    ``mean_per_class_acc`` (all three, whatever the metric), ``loss``, ``keep_ratio_per_layer``, ``n``, ``ignored``, ``nan_rows`` and, with
+    the FLOPs table, ``gflops``."""
+    model.eval()
+    stats = None
+    for _, images, target, _ in DevicePrefetcher(data_loader, device, _verified_copy_stream(model)):
+        if video:
+            B, V = images.shape[0], images.shape[1]
+            output, aux = model(images.flatten(0, 1))
+            output = output.view(B, V, -1).mean(dim=1)   # [B, C]: small
+        else:
+            output, aux = model(images)
+        ts = aux["token_select"]
+        if stats is None:
+            stats = StreamingEval(output.shape[1], layers=ts.shape[1], tokens=ts.shape[2], device=output.device)
+        stats.update(output.float(), target, ts.float())
+    if stats is None:
+        raise DyTError("evaluate: the data loader yielded no batch")
+    if is_dist_avail_and_initialized():
+        stats.all_reduce()
+    res = stats.result(flops_dict=flops_dict, base_flops=base_flops)
+    status = {}
+    metric = getattr(args, "metric", "accuracy")
+    if metric == "accuracy":
+        status["metric"] = res["acc1"]
+    elif metric == "mean_per_class_acc":
+        status["metric"] = res["mean_per_class_acc"]
+    status.update(res)
+    if logger is not None:
+        logger.info("* metric %.3f keep ratio %.4f loss %.4f" % (status["metric"], status["keep_ratio"], status["loss"]))
+    return status
+
+
 @torch.no_grad()
 def evaluate(data_loader, model, device, logger=None, base_flops=None, flops_dict=None, args=None):
     """Reference engine_finetune.py:208-279: eval-mode forward over the loader, gather across ranks,
-    top-1 (or mean-per-class) accuracy in ``status["metric"]``."""
+    top-1 (or mean-per-class) accuracy in ``status["metric"]``.  With ``args.stream_eval`` (or DYT_STREAM_EVAL=1) the statistics are folded into
+    a fixed-size device state batch by batch instead (``_evaluate_streaming``)."""
+    if stream_eval_requested(args):
+        return _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_dict, args, video=False)
     model.eval()
     token_select, targets, predictions = [], [], []
     for _, images, target, _ in DevicePrefetcher(data_loader, device, _verified_copy_stream(model)):
@@ -827,7 +874,10 @@ def evaluate(data_loader, model, device, logger=None, base_flops=None, flops_dic
 @torch.no_grad()
 def evaluate_video(data_loader, model, device, logger=None, base_flops=None, flops_dict=None, args=None):
     """Reference engine_finetune.py:281-356: every sample carries V views [B,V,c,t,h,w]; views are folded into the batch,
-    the per-view logits averaged per sample (:302-305), then the same gather + accuracy as ``evaluate``."""
+    the per-view logits averaged per sample (:302-305), then the same gather + accuracy as ``evaluate``.  ``args.stream_eval`` /
+    DYT_STREAM_EVAL=1: as in ``evaluate``."""
+    if stream_eval_requested(args):
+        return _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_dict, args, video=True)
     model.eval()
     token_select, targets, predictions = [], [], []
     for _, images, target, _ in DevicePrefetcher(data_loader, device, _verified_copy_stream(model)):

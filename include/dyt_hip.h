@@ -408,6 +408,37 @@ int dyt_mix_images(const void* src, float* dst, int count, int frames, int src_k
  * rows even, 1 <= num_classes <= 65 536.  One launch on `stream`. */
 int dyt_mix_targets(const int64_t* labels, float* out, int rows, int num_classes, const void* params_dev, void* stream);
 
+/* Streaming evaluation statistics (csrc/eval_stats.h, csrc/eval_stats.hip): a batch of logits, labels and token masks is folded into a
+ * fixed-size device-resident state, so that an evaluation loop keeps no per-sample tensor.  Two context-free entries, added without an ABI
+ * version change (the version stays 5) and discovered by their symbols; pure fp32 / integer, the same bits from both libraries.
+ * The state is ADDITIVE -- every entry accumulates, the caller zeroes it, ranks merge with a SUM all-reduce:
+ *   counts     int64 [DYT_EVAL_OFF_KEEP + layers * (tokens + 1)]:
+ *                [0, 8)   head: rows counted, rows ignored, rows holding a NaN, mask rows (images) counted, 4 spare words
+ *                [8, 24)  rank histogram: bin r < 15 = exactly r classes rank ahead of the label, bin 15 = 15 or more
+ *                [24, ..) keep histogram [layers][tokens + 1]: (image, layer) pairs by their number of non-zero mask entries
+ *   per_class  int64 [2 * classes] or NULL: per-class totals, then per-class top-1 hits
+ *   loss_sum   double [1]: sum of the row losses
+ * Rows: logits fp32 [rows, ld] (ld >= classes elements between rows; any 4-byte aligned base -- 16-byte loads are used for the part of each row
+ * that allows them), labels int64 [rows].  A label outside [0, classes) makes the row IGNORED: counted as such, excluded from everything
+ * else, row_rank -1, row_loss 0.  A row holding a NaN is counted (rows, NaN word, last rank bin, its class total), is no hit at any k
+ * (row_rank = classes) and stays out of loss_sum (row_loss 0).  Otherwise rank = #{j : x_j > x_t} + #{j < t : x_j == x_t} and
+ * row_loss = -((x_t - max) - log(sum_j exp(x_j - max))).  row_rank int32 [rows] and row_loss fp32 [rows] are written for every row.
+ * Two launches on `stream`: the row kernel (each logit read once), then ONE workgroup that folds the row results (loss in double in a
+ * fixed order, integer adds elsewhere): the state is bit-reproducible run to run.
+ * Masks: token_select fp32 [images, layers, tokens]; one launch.
+ * DYT_ERR_ARG with a text, before anything is enqueued: a null pointer (per_class excepted), rows / images outside 1 ... 2^20, classes outside
+ * 1 ... 65 536, ld < classes, layers outside 1 ... 64, tokens outside 1 ... 1024, counts / labels / loss_sum / per_class not 8-byte aligned. */
+#define DYT_EVAL_HEAD_WORDS 8
+#define DYT_EVAL_ROWS 0
+#define DYT_EVAL_IGNORED 1
+#define DYT_EVAL_NAN_ROWS 2
+#define DYT_EVAL_MASK_ROWS 3
+#define DYT_EVAL_RANK_BINS 16
+#define DYT_EVAL_OFF_RANK 8
+#define DYT_EVAL_OFF_KEEP 24
+int dyt_eval_rows(const float* logits, int64_t ld, const int64_t* labels, int rows, int classes, int64_t* counts, int64_t* per_class, double* loss_sum, int32_t* row_rank, float* row_loss, void* stream);
+int dyt_eval_keep(const float* token_select, int images, int layers, int tokens, int64_t* counts, void* stream);
+
 /* torch.optim.AdamW over the flat trainable buffer -- main_image.py:285; the gradient is first
  * multiplied by grad_scale (1/world_size after a SUM all-reduce).  `step` is 1-based. */
 int dyt_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
