@@ -267,6 +267,39 @@ def mix_targets(labels, num_classes, params, out=None):
     return out
 
 
+def erase_images(images, table, frames=1, norm=None, mix_params=None, out=None):
+    """dyt_erase_images: a device batch -- fp32 [n,3,224,224], uint8 [n,3,224,224] or uint8 [n,224,224,3] -- with the boxes of the device
+    table ``table`` (int32 words: csrc/erase.h, util.erasing.EraseDraw.words()) erased -> fp32 [n,3,224,224], on torch's current stream.
+    uint8 images are normalised with ``norm`` = (mean, std) first.  ``mix_params`` (int32[16], csrc/mix.h MixParams): the erased batch is
+    then mixed with its erased mirror.  The table must hold a row for every image."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_erase_images"):
+        raise DyTError("this libdyt_hip has no dyt_erase_images (on-device random erasing): rebuild it")
+    layout = byte_image_layout(images)
+    if layout is None and not (images.dtype == torch.float32 and tuple(images.shape[1:]) == (3, 224, 224)):
+        raise DyTError("erase_images takes fp32 [n,3,224,224] or uint8 images (got %s %s)" % (images.dtype, tuple(images.shape)))
+    if layout is not None and norm is None:
+        raise DyTError("erase_images: uint8 images need norm=(mean, std) (the model's input_norm)")
+    n, frames = int(images.shape[0]), int(frames)
+    if frames < 1 or n < 1 or n % frames != 0:
+        raise DyTError("erase: the image count is not a positive multiple of frames (%d images, %d frame(s) per clip)" % (n, frames))
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= 16 + 20 * n):
+        raise DyTError("erase table: a contiguous int32 device tensor of 16 + 20 x %d words at least (util.erasing.EraseDraw.words(capacity)); "
+                       "the kernels may read a row for every image" % n)
+    if mix_params is not None and (n // frames) % 2 != 0:
+        raise DyTError("mix: an odd number of images / clips cannot be paired (%d images, %d frame(s) per clip)" % (n, frames))
+    images = images.contiguous()
+    if out is None:
+        out = torch.empty(n, 3, 224, 224, device=images.device, dtype=torch.float32)
+    kind = 0 if layout is None else (2 if layout == "nhwc" else 1)
+    mean, std = (float3(norm[0]), float3(norm[1])) if layout is not None else (None, None)
+    with torch.cuda.device(images.device):
+        check(L.dyt_erase_images(ptr(images), ptr(out), n, frames, kind, mean, std, ptr(table),
+                                 None if mix_params is None else _mix_params_ptr(mix_params), stream_ptr()), L)
+    return out
+
+
 # csrc/eval_stats.h / DYT_EVAL_* of include/dyt_hip.h: the int64 `counts` state of the streaming evaluation
 EVAL_HEAD_WORDS, EVAL_ROWS, EVAL_IGNORED, EVAL_NAN_ROWS, EVAL_MASK_ROWS = 8, 0, 1, 2, 3
 EVAL_RANK_BINS, EVAL_OFF_RANK, EVAL_OFF_KEEP = 16, 8, 24
@@ -353,6 +386,8 @@ SYMBOLS = {
     "dyt_set_mix": (_i, [_vp, _vp, _i]),
     "dyt_mix_images": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _vp]),
     "dyt_mix_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "dyt_set_erase": (_i, [_vp, _vp, _i, _i]),
+    "dyt_erase_images": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _vp, _vp]),
     "dyt_eval_rows": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dyt_eval_keep": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -405,6 +440,7 @@ SYMBOLS = {
 # Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
+                    "dyt_set_erase", "dyt_erase_images",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
 
 _lib16 = None

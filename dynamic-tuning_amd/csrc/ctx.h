@@ -163,6 +163,9 @@ struct dyt_ctx {
     // dyt_set_mix: while mix_params (a DEVICE block the kernels read at run time) is set, forward_impl launches the mixing im2col and
     // dyt_step_fwd_bwd writes the class-probability rows into mix_soft ([max_batch][num_classes], allocated by the first dyt_set_mix) for its loss
     const MixParams* mix_params = nullptr; int mix_frames = 1; float* mix_soft = nullptr; size_t mix_soft_bytes = 0;
+    // dyt_set_erase: while erase_table (a DEVICE table the kernels read at run time, csrc/erase.h) is set, the TRAINING passes of forward_impl
+    // launch the erasing im2col (which also mixes when mix_params is set); erase_capacity = the rows the table's allocation holds
+    const void* erase_table = nullptr; int erase_capacity = 0; int erase_frames = 1;
     bool split16 = false;       // fp32 mode: frozen-weight GEMMs as three 16-bit MFMA products (DYT_OPT_F32_SPLIT16)
     void* pe_w3 = nullptr;
     // 16-bit modes: LayerNorm-2 is not a kernel -- the proj epilogue emits per-row partial statistics of u, fc1 contracts the 16-bit copy
@@ -230,6 +233,8 @@ int set_matrix(dyt_ctx* c, const float* src, void* w, void* wT, int N, int K, hi
 hipEvent_t get_event(dyt_ctx* c);
 // mix.hip
 int check_mix_batch(const dyt_ctx* c, int batch);   // mix on: an image count that cannot be paired, DYT_ERR_ARG with a text
+// erase.hip
+int check_erase_batch(const dyt_ctx* c, int batch);   // erasing on: a batch the table has no rows for, DYT_ERR_ARG with a text
 // forward.hip
 int prep_adapters(dyt_ctx* c, const float* trainable, hipStream_t s);
 int prep_pool(dyt_ctx* c, const float* tr, hipStream_t s);

@@ -172,6 +172,8 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
     { int rc = check_image_input(flags, images); if (rc) return rc; }   // DYT_F_IMAGES_U8 / _NHWC: `images` is a byte batch
     const bool mix = c->mix_params && !(flags & DYT_F_TOKENS_IN);   // dyt_set_mix: the embedding load mixes every image with its partner
     if (mix) { int rc = check_mix_batch(c, B); if (rc) return rc; }
+    const bool erase = c->erase_table && (flags & DYT_F_TRAINING) && !(flags & DYT_F_TOKENS_IN);   // dyt_set_erase: training passes erase in the same load; an eval forward never does
+    if (erase) { int rc = check_erase_batch(c, B); if (rc) return rc; }
     if (flags & DYT_F_SAVE) { int rc = refuse_inference(c, slot > 0 ? "dyt_forward with DYT_F_SAVE into a slot > 0" : "dyt_forward with DYT_F_SAVE"); if (rc) return rc; }
     if ((flags & DYT_F_TRAINING) && c->drop_path_rate > 0.f) { int rc = refuse_inference(c, "a training forward with stochastic depth"); if (rc) return rc; }
     const int P = c->prec, depth = c->cfg.depth, M = B * NT, r = c->cfg.ffn_num;
@@ -215,7 +217,12 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
         DYT_HIP_CHECK(hipMemcpyAsync(S.xs[0], images, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else if (!share0) {
         // patch embedding: im2col + GEMM (+bias +pos_embed), cls rows
-        if (mix && (flags & DYT_F_IMAGES_U8))
+        if (erase && (flags & DYT_F_IMAGES_U8))
+            RUN(2, 0, launch_im2col_erase_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, c->erase_frames,
+                                             c->erase_table, c->erase_capacity, mix ? c->mix_params : nullptr, s));
+        else if (erase)
+            RUN(2, 0, launch_im2col_erase(P, images, T.xn, B, c->erase_frames, c->erase_table, c->erase_capacity, mix ? c->mix_params : nullptr, s));
+        else if (mix && (flags & DYT_F_IMAGES_U8))
             RUN(2, 0, launch_im2col_mix_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, c->mix_frames, c->mix_params, s));
         else if (mix)
             RUN(2, 0, launch_im2col_mix(P, images, T.xn, B, c->mix_frames, c->mix_params, s));

@@ -1,5 +1,5 @@
-// Device helpers shared by the kernels that read byte images (input_u8.hip, mix.hip): the 3 x 256 table of input_norm_value in LDS, byte
-// extraction from 16- and 48-byte runs, and the 16-element store.  Private to those two units.
+// Device helpers shared by the kernels that read byte images (input_u8.hip, mix.hip, erase.hip): the 3 x 256 table of input_norm_value in LDS, byte
+// extraction from 16- and 48-byte runs, and the 16-element store.  Private to those units.
 #pragma once
 #include "ctx.h"
 

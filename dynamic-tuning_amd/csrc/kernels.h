@@ -5,6 +5,7 @@
 #include "attn_route.h"
 #include "input_norm.h"
 #include "mix.h"
+#include "erase.h"
 
 namespace dyt {
 
@@ -235,6 +236,13 @@ int launch_im2col_mix_u8(int precision, const uint8_t* images, int nhwc, const I
                          const MixParams* params, hipStream_t s);
 int launch_mix_images(const void* src, float* dst, int count, int frames, int src_kind, const InputNorm& nm, const MixParams* params, hipStream_t s);
 int launch_mix_targets(const int64_t* labels, float* out, int rows, int num_classes, const MixParams* params, hipStream_t s);
+// erase.hip: the same loads with Random Erasing applied first (table in device memory, `capacity` rows), then the mix when `mix` is set
+int launch_im2col_erase(int precision, const float* images, void* out, int batch, int frames, const void* table, int capacity,
+                        const MixParams* mix, hipStream_t s);
+int launch_im2col_erase_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, int frames,
+                           const void* table, int capacity, const MixParams* mix, hipStream_t s);
+int launch_erase_images(const void* src, float* dst, int count, int frames, int src_kind, const InputNorm& nm, const void* table, int capacity,
+                        const MixParams* mix, hipStream_t s);
 int check_image_input(int flags, const void* images);   // DYT_F_IMAGES_U8 / _NHWC of a pass: flag combination and pointer alignment, DYT_ERR_ARG with a text
 int launch_cls_rows(const float* cls, const float* pos, float* x0, int batch, hipStream_t s);
 // fp32 -> AT copy (n elements)

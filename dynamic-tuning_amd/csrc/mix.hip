@@ -1,5 +1,6 @@
 // On-device Mixup / CutMix, fused into the patch-embedding load (dyt_set_mix) and as two context-free entries (dyt_mix_images,
-// dyt_mix_targets).  The scalar formula, the pairing, the source predicate and every argument check are mix.h.
+// dyt_mix_targets).  The scalar formula, the pairing, the source predicate and every argument check are mix.h.  The run-level helpers
+// (mix_run, unpack, lookup) are mix_dev.h, shared with erase.hip.
 //
 //   im2col_mix_kernel<AT>            fp32 [B,3,224,224] -> the EPI_EMBED GEMM's A operand: im2col_kernel's work items (4 pixels of one image
 //                                    row, one 16-byte load) and element order
@@ -14,42 +15,11 @@
 // columns meet [xl, xh), never for identity (whose output is a copy of the own pixels: -0.0, NaN and inf pass, nothing of the partner
 // leaks in).  Nothing read from the block is used as an index: a block with any content cannot make a kernel leave its buffers.  One
 // writer per output element, no atomics.
-#include "input_u8_dev.h"
+#include "mix_dev.h"
 
 namespace dyt {
 
 #define LAUNCH_CHECK() DYT_HIP_CHECK(hipGetLastError())
-
-namespace {
-
-constexpr size_t PLANE = (size_t)IMG * IMG;
-
-// v: N own pixels of row y from column x0; w: the partner's.  Called only when mix_run_needs_partner.
-template <int N>
-__device__ __forceinline__ void mix_run(float (&v)[N], const float (&w)[N], const MixParams& p, int y, int x0) {
-    if (p.mode == MIX_MIXUP) {
-#pragma unroll
-        for (int j = 0; j < N; ++j) v[j] = mix_value(v[j], w[j], p.lam_f, p.oml_f);
-    } else {
-#pragma unroll
-        for (int j = 0; j < N; ++j)
-            if (mix_from_partner(p.mode, y, x0 + j, p.yl, p.yh, p.xl, p.xh)) v[j] = w[j];
-    }
-}
-
-__device__ __forceinline__ void unpack(float (&v)[4], const float4& q) { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-
-// 16 pixels of channel c (NCHW run: the 16 bytes of w; NHWC run: every third byte of the 48) through the table
-__device__ __forceinline__ void lookup(float (&v)[16], const float* tab, const uint4& w, int c) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = tab[c * 256 + byte_of(w, j)];
-}
-__device__ __forceinline__ void lookup(float (&v)[16], const float* tab, const uint4 (&w)[3], int c) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = tab[c * 256 + byte_of(w, j * 3 + c)];
-}
-
-}  // namespace
 
 template <class AT>
 __global__ __launch_bounds__(256) void im2col_mix_kernel(const float* __restrict__ img, AT* __restrict__ out, int batch, int frames,

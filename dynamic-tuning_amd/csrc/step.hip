@@ -113,6 +113,7 @@ extern "C" int dyt_step_fwd_bwd(dyt_ctx* c, const float* images, const int64_t* 
         if (c->soft_targets) { set_error("dyt_step_fwd_bwd: mix is on (dyt_set_mix) and class-probability targets are set (dyt_set_soft_targets)"); return DYT_ERR_STATE; }
         int rc = check_mix_batch(c, batch); if (rc) return rc;
     }
+    { int rc = check_erase_batch(c, batch); if (rc) return rc; }   // dyt_set_erase: a batch the table has no rows for
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int depth = c->cfg.depth;
     const size_t nz = (size_t)depth * batch * NP;        // per-pass noise stride

@@ -18,6 +18,7 @@ import torch.distributed as dist
 import util.lr_sched as lr_sched
 from _lib import DyTError
 from util.mixup import DeviceMixup
+from util.erasing import DeviceRandomErasing
 from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
@@ -511,7 +512,7 @@ def step_seed(epoch, it, base=None):
 
 def train_step(model, samples, targets, optimizer, criterion=None, losses_out=None, gumbel=None, keep_mask=None,
                seed=0, target_ratio=None, token_minimal=None, token_minimal_weight=None, accumulate=False, update=True,
-               accum_iter=1, max_norm=0.0, graph=False, mix=None):
+               accum_iter=1, max_norm=0.0, graph=False, mix=None, erase=None):
     """One fused step (reference engine_finetune.py:47-79) on device tensors; returns the device
     tensor of loss components [loss, base, token, teacher, distillation, keep ratio, kept, 0].
     graph=True replays the forward+backward from a captured hipGraph (on-device noise only).
@@ -519,7 +520,9 @@ def train_step(model, samples, targets, optimizer, criterion=None, losses_out=No
     CrossEntropyLoss terms then take the soft form (C ABI dyt_set_soft_targets).
     ``mix``: a util.mixup.MixDraw (``DeviceMixup.draw()``) -- ``samples`` is the UNMIXED batch (bytes stay bytes) and ``targets`` its integer
     labels; the library mixes inside the patch-embedding load and writes the class-probability targets itself (C ABI dyt_set_mix), the
-    criterion's own label_smoothing on top.  graph=True stays honoured: the draw is device data of the captured step."""
+    criterion's own label_smoothing on top.  graph=True stays honoured: the draw is device data of the captured step.
+    ``erase``: a util.erasing.EraseDraw (``DeviceRandomErasing.draw_for(images, frames)``) -- the library erases the boxes inside the same
+    load, before the mix (C ABI dyt_set_erase); ``samples`` stays as it is, and graph=True stays honoured."""
     m = getattr(model, "module", model)
     if getattr(m, "inference_only", False):
         raise DyTError("train_step: the model was built with inference_only (eval forwards only); build it without inference_only to train")
@@ -527,6 +530,11 @@ def train_step(model, samples, targets, optimizer, criterion=None, losses_out=No
     eng = m.engine(samples.shape[0], samples.device)
     # nn.CrossEntropyLoss(label_smoothing = e) is the soft form with t (1 - e) + e / C (torch applies the same map to class-probability targets)
     smooth = float(getattr(getattr(criterion, "base_criterion", None), "label_smoothing", 0.0) or 0.0)
+    if erase is not None:
+        if erase.images() != samples.shape[0] or (erase.cube and erase.frames != eng.frames):
+            raise DyTError("erase: the draw covers %d images (clips of %d), the batch has %d (clips of %d)" % (
+                erase.images(), erase.frames if erase.cube else 1, samples.shape[0], eng.frames))
+    eng.set_erase(erase)
     if mix is not None:
         if targets.dim() != 1 or targets.is_floating_point():
             raise DyTError("train_step(mix=...) takes the integer labels of the unmixed batch (got %s %s)" % (targets.dtype, tuple(targets.shape)))
@@ -691,15 +699,44 @@ def _verified_copy_stream(model):
     return lambda samples=None, targets=None: getattr(getattr(m, "_engine", None), "_copy_stream_probe", (None, None))[0]
 
 
+def _device_erasing(args, cube_default=False):
+    """``args.random_erasing``, or with ``args.device_erase`` a DeviceRandomErasing of the reference's create_transform arguments
+    (util/datasets.py:43-45: re_prob = args.reprob, re_mode = args.remode, re_count = args.recount), or None."""
+    if args is None:
+        return None
+    eraser = getattr(args, "random_erasing", None)
+    if eraser is not None:
+        if not isinstance(eraser, DeviceRandomErasing):
+            raise DyTError("args.random_erasing must be a util.erasing.DeviceRandomErasing (got %r)" % (type(eraser),))
+        return eraser
+    if not getattr(args, "device_erase", False):
+        return None
+    cached = getattr(args, "_device_erasing", None)
+    if cached is None:
+        prob = float(getattr(args, "reprob", 0.0) or 0.0)
+        if prob <= 0.0:
+            return None
+        cached = DeviceRandomErasing(probability=prob, mode=getattr(args, "remode", "const") or "const",
+                                     max_count=int(getattr(args, "recount", 1) or 1), cube=cube_default)
+        try:
+            args._device_erasing = cached   # one generator for the whole run
+        except AttributeError:
+            pass
+    return cached
+
+
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler=None, max_norm=0,
-                    mixup_fn=None, log_writer=None, args=None, logger=None):
+                    mixup_fn=None, log_writer=None, args=None, logger=None, _video=False):
     """Reference engine_finetune.py:16-106.  ``optimizer`` is the ``torch.optim.AdamW`` the drivers build (main_image.py:285;
     adopted by a FusedAdamW on first use, ``as_fused``) or a FusedAdamW; ``loss_scaler`` (the drivers' ``NativeScaler()``,
     main_image.py:290) is bound to that optimizer's gradient-scale state -- the loss scaling itself (the reference's GradScaler,
     misc.py:252-272) is the library's power-of-two scale on 16-bit gradient operands plus the device-side overflow guard;
     ``max_norm`` (--clip_grad) clips the global gradient norm on the device before the update.  ``args.hip_graph`` replays the
-    step from a hipGraph."""
+    step from a hipGraph.  ``args.random_erasing`` (a util.erasing.DeviceRandomErasing; or ``args.device_erase`` true, which builds one from
+    ``args.reprob`` / ``args.remode`` / ``args.recount``, the names util/datasets.py reads): Random Erasing on the device, inside the fused
+    step's image load and before the mix of a DeviceMixup; with any other callable ``mixup_fn`` the batch is erased first (fp32 out)."""
     optimizer = as_fused(optimizer, model)
+    eraser = _device_erasing(args, cube_default=_video)
     if loss_scaler is not None and hasattr(loss_scaler, "bind"):
         loss_scaler.bind(optimizer)
     accum_iter = max(1, int(getattr(args, "accum_iter", 1) or 1)) if args is not None else 1
@@ -722,7 +759,12 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         keep_mask = extra[1].to(device).contiguous() if len(extra) > 1 and extra[1] is not None else None
         if it % accum_iter == 0:   # per-iteration schedule, reference :43-46
             lr = lr_sched.adjust_learning_rate(optimizer, it / nsteps + epoch, args)
-        mix = None
+        mix, erase = None, None
+        if eraser is not None and (mixup_fn is None or isinstance(mixup_fn, DeviceMixup)):   # erased inside the fused step: the batch stays as it is
+            frames = 1 if samples.dim() != 5 else samples.shape[1 if tuple(samples.shape[2:]) == (224, 224, 3) else 2]   # clips [b,c,t,h,w] / bytes [b,t,h,w,c]
+            erase = eraser.draw_for(samples.shape[0] * frames, frames)
+        elif eraser is not None:   # any other mixup_fn mixes on its own: the erasing comes first, as fp32 images
+            samples = eraser(samples, norm=getattr(m, "input_norm", None))
         if isinstance(mixup_fn, DeviceMixup):   # the mix happens inside the fused step: the batch stays as it is (bytes stay bytes), labels stay integers
             mix = mixup_fn.draw()
         elif mixup_fn is not None:   # reference :44-45 (timm.data.Mixup or any callable of that shape): mixed samples, class-probability targets
@@ -731,7 +773,7 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
             samples, targets = mixup_fn(samples, targets)
         train_step(model, samples, targets, optimizer, criterion, losses_out=step_losses, seed=step_seed(epoch, it),
                    gumbel=gumbel, keep_mask=keep_mask, accumulate=(it % accum_iter != 0), update=((it + 1) % accum_iter == 0),
-                   accum_iter=accum_iter, max_norm=max_norm or 0.0, graph=use_graph, mix=mix)
+                   accum_iter=accum_iter, max_norm=max_norm or 0.0, graph=use_graph, mix=mix, erase=erase)
         acc += step_losses
         pending += 1
         if (it + 1) % print_freq == 0 or it + 1 == nsteps:
@@ -758,6 +800,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     if mixup_fn is not None and getattr(m, "_engine", None) is not None:
         m._engine.set_mix(None)            # evaluation / the next caller's passes see their images unmixed ...
         m._engine.set_soft_targets(None)   # ... and use their integer labels
+    if eraser is not None and getattr(m, "_engine", None) is not None:
+        m._engine.set_erase(None)          # ... and unerased, whatever flags the next caller's passes carry
     optimizer.publish_torch_state()   # an adopted torch.optim.AdamW now reports this epoch's moments / step count (misc.save_model)
     if is_dist_avail_and_initialized():  # metric_logger.synchronize_between_processes(), reference :104
         t = torch.tensor([stats[k] for k in LOSS_KEYS], device=device, dtype=torch.float64)
@@ -772,7 +816,7 @@ def train_video_one_epoch(model, criterion, data_loader, optimizer, device, epoc
     """Reference engine_finetune.py:109-203: the video loop is the image loop with clip tensors
     [b,c,t,h,w]; the model folds the frames into the batch and pools them per clip."""
     return train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler, max_norm, mixup_fn,
-                           log_writer, args, logger)
+                           log_writer, args, logger, _video=True)   # (args.device_erase: cube, as the reference's clip pipeline erases)
 
 
 def all_gather_concat(tensor):

@@ -109,6 +109,7 @@ class DyTEngine:
         self.grad_scale_log2 = 12 if self.precision in (PREC_FP16, PREC_FP16X3H, PREC_FP16F8, PREC_FP16X3Q) else None
         self.input_norm = INPUT_NORMS["imagenet"]   # what the context normalises uint8 images with (set_input_norm); the library's default
         self._mix_on, self._mix_dev = False, None   # set_mix: the context mixes in the embedding load; the static device block of the draws
+        self._erase_on, self._erase_dev = False, None   # set_erase: the training passes erase in the embedding load; the static device table
 
     def _ck(self, rc):
         check(rc, self.L)
@@ -293,7 +294,7 @@ class DyTEngine:
         # step is captured with the input norm of its time)
         key = (tuple(images.shape), images.dtype, self.input_norm if images.dtype == torch.uint8 else None, tuple(targets.shape),
                float(target_ratio), float(loss_ratio), float(token_minimal), float(token_minimal_weight), bool(masked_dense), bool(accumulate),
-               bool(self._mix_on))   # mix on / off are two graphs (other kernels); the draw itself is device data, not part of the key
+               bool(self._erase_on), bool(self._mix_on))   # erase / mix on / off are other graphs (other kernels); the draws themselves are device data, not part of the key
         ent = self._graphs.get(key)
         cur = torch.cuda.current_stream(self.device)
         if ent is None:
@@ -618,6 +619,57 @@ class DyTEngine:
         from _lib import mix_targets
         params = torch.frombuffer(bytearray(draw.words(criterion_smoothing)), dtype=torch.int32).to(self.device)
         return mix_targets(labels, self.num_classes, params)
+
+    # ---- on-device random erasing ----------------------------------------------------------------
+    def set_erase(self, draw):
+        """dyt_set_erase.  ``draw`` (util.erasing.EraseDraw, e.g. ``DeviceRandomErasing.draw_for(batch, frames)``): the TRAINING passes
+        enqueued from now on erase every image inside the patch-embedding load, before the mix of ``set_mix``; eval forwards never erase.
+        None: off.  Like ``set_mix``: ONE static device table (a row for each of max_batch images), a small pinned host ring and a
+        non-blocking copy on the current stream, outside any captured graph -- one graph serves every draw."""
+        if draw is None:
+            if self._erase_on:
+                self._ck(self.L.dyt_set_erase(self.h, None, 0, self.frames))
+                self._erase_on = False
+            return
+        self._refuse_inference("set_erase")
+        if not hasattr(self.L, "dyt_set_erase"):
+            raise DyTError("this libdyt_hip has no dyt_set_erase (on-device random erasing): rebuild it")
+        from util.erasing import table_words
+        if draw.cube and draw.frames != self.frames:
+            raise DyTError("erase: the draw's clips have %d frame(s), the engine folds %d" % (draw.frames, self.frames))
+        if draw.images() > int(self.cfg.max_batch):
+            raise DyTError("erase: the draw covers %d images, the engine's max_batch is %d" % (draw.images(), int(self.cfg.max_batch)))
+        cap = int(self.cfg.max_batch)
+        words = draw.words(cap)
+        if self._erase_dev is None:
+            self._erase_dev = torch.zeros(table_words(cap), dtype=torch.int32, device=self.device)
+            self._erase_ring = torch.zeros(self.MIX_RING, table_words(cap), dtype=torch.int32).pin_memory()
+            self._erase_events = [None] * self.MIX_RING
+            self._erase_at = 0
+        k = self._erase_at
+        self._erase_at = (k + 1) % self.MIX_RING
+        if self._erase_events[k] is not None:
+            self._erase_events[k].synchronize()   # the copy that read this slot MIX_RING draws ago: long complete, this does not wait
+        self._erase_ring[k].copy_(torch.frombuffer(bytearray(words), dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            self._erase_dev.copy_(self._erase_ring[k], non_blocking=True)
+            if self._erase_events[k] is None:
+                self._erase_events[k] = torch.cuda.Event()
+            self._erase_events[k].record()
+            if not self._erase_on:
+                self._ck(self.L.dyt_set_erase(self.h, ptr(self._erase_dev), cap, self.frames))
+                self._erase_on = True
+
+    def erase_images(self, images, draw, mix=None):
+        """The images the fused path computes with, as a plain fp32 batch [n,3,224,224] (dyt_erase_images with this engine's frames and
+        input norm; ``mix``: a MixDraw applied after the erasing): the reference point of ``set_erase`` (+ ``set_mix``)."""
+        from _lib import erase_images
+        n = int(images.shape[0])
+        if draw.images() != n:
+            raise DyTError("erase: the draw covers %d images, the batch has %d" % (draw.images(), n))
+        table = torch.frombuffer(bytearray(draw.words(n)), dtype=torch.int32).to(self.device)
+        params = None if mix is None else torch.frombuffer(bytearray(mix.words()), dtype=torch.int32).to(self.device)
+        return erase_images(images, table, frames=self.frames, norm=self.input_norm, mix_params=params)
 
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on):

@@ -408,6 +408,28 @@ int dyt_mix_images(const void* src, float* dst, int count, int frames, int src_k
  * rows even, 1 <= num_classes <= 65 536.  One launch on `stream`. */
 int dyt_mix_targets(const int64_t* labels, float* out, int rows, int num_classes, const void* params_dev, void* stream);
 
+/* On-device Random Erasing (the "erase a normalised batch" RandomErasing of timm / SlowFast, restated in csrc/erase.h), fused into the
+ * patch-embedding load.  Added like the mix entries: no ABI version change, no flag, discovered by symbol; "erase on" is context state.
+ * The draw lives in DEVICE memory: table_dev points to 32-bit words, 16-byte aligned --
+ *   16 header words: mode (0 off, 1 const = 0.0f, 2 rand = one N(0,1) colour per image, box and channel, 3 pixel = one N(0,1) value per
+ *   pixel and channel), frames, cube (!= 0: one row per clip, shared by its frames), units (rows in use), the 64-bit noise seed as two
+ *   words, 10 reserved words;
+ *   then one row of 20 words per unit: the box count n (0..4), four boxes (top, h, left, w), 3 unused words
+ * -- and is read by the kernels when they RUN: a captured step replayed after the table was overwritten erases with the new draw.  Nothing
+ * in the table is used as an index: the row is chosen from the image number, n is clamped, boxes are only compared against.  A later box
+ * overwrites an earlier one.  The noise is Philox4x32-10 keyed by (seed, image, channel, row, column) through Box-Muller (csrc/erase.h).
+ * dyt_set_erase: while table_dev is set, every TRAINING pass of this context that takes images (dyt_forward with DYT_F_TRAINING,
+ * dyt_step_fwd_bwd; uint8 or fp32) erases them where the embedding operand is produced, BEFORE the mix of dyt_set_mix (the partner's
+ * erased pixels are what is blended in) -- bit for bit the float path on dyt_erase_images' output.  Forwards without DYT_F_TRAINING never
+ * erase.  units_capacity = the rows the allocation behind table_dev holds; the pointer is kept, not copied; NULL turns erasing off, and the
+ * passes launch exactly the kernels they launched before.  Refused with a text, before anything is enqueued: an inference_only context, a
+ * misaligned pointer, `frames` other than the context's, units_capacity < 1, and (by the pass) a batch of more images than units_capacity. */
+int dyt_set_erase(dyt_ctx* ctx, const void* table_dev, int units_capacity, int frames);
+/* The erased images as a plain fp32 batch, without a context: src as in dyt_mix_images -> dst fp32 [count,3,224,224].  The table must hold
+ * a row for every image (count rows at least).  mix_params_dev: NULL, or a MixParams block -- the erased batch is then mixed with its
+ * erased mirror (count an even number of clips).  One launch on `stream`. */
+int dyt_erase_images(const void* src, float* dst, int count, int frames, int src_kind, const float mean[3], const float std[3], const void* table_dev, const void* mix_params_dev, void* stream);
+
 /* Streaming evaluation statistics (csrc/eval_stats.h, csrc/eval_stats.hip): a batch of logits, labels and token masks is folded into a
  * fixed-size device-resident state, so that an evaluation loop keeps no per-sample tensor.  Two context-free entries, added without an ABI
  * version change (the version stays 5) and discovered by their symbols; pure fp32 / integer, the same bits from both libraries.
