@@ -300,6 +300,66 @@ def erase_images(images, table, frames=1, norm=None, mix_params=None, out=None):
     return out
 
 
+RESAMPLE_HEADER_WORDS, RESAMPLE_ROW_WORDS, RESAMPLE_COEFF_WORDS, RESAMPLE_MAX_SIDE = 16, 12, 2 * 13 * 224, 4096   # csrc/resample.h
+
+
+def _resample_args(L, pixels, table):
+    import torch
+    if not hasattr(L, "dyt_resample_u8"):
+        raise DyTError("this libdyt_hip has no dyt_resample_u8 (device crop / resize): rebuild it")
+    if not (torch.is_tensor(pixels) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 4 and pixels.shape[3] == 3):
+        raise DyTError("resample takes a uint8 device batch [B, Hs, Ws, 3] (got %s %s); planar sources and clips are not implemented" % (
+            getattr(pixels, "dtype", type(pixels)), tuple(getattr(pixels, "shape", ()))))
+    n, hs, ws = int(pixels.shape[0]), int(pixels.shape[1]), int(pixels.shape[2])
+    if n < 1 or hs < 1 or ws < 1 or hs > RESAMPLE_MAX_SIDE or ws > RESAMPLE_MAX_SIDE:
+        raise DyTError("resample: a batch of %d images of %d x %d (at least one image, sides 1 to %d)" % (n, hs, ws, RESAMPLE_MAX_SIDE))
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and
+            table.numel() >= RESAMPLE_HEADER_WORDS + RESAMPLE_ROW_WORDS * n):
+        raise DyTError("resample table: a contiguous int32 device tensor of 16 + 12 x %d words at least (util.crop.CropDraw.words(capacity))" % n)
+    return n, hs, ws, (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+
+
+def resample_u8(pixels, table, draw=None, out=None, scratch=None):
+    """dyt_resample_u8: a uint8 device batch [B, Hs, Ws, 3] (channels-last, padded) cropped, resized with Pillow's bicubic arithmetic, windowed
+    and mirrored as the rows of the device table ``table`` (int32 words: csrc/resample.h, util.crop.CropDraw.words()) say -> uint8
+    [B, 224, 224, 3], on torch's current stream.  ``draw`` (the CropDraw behind the table): checked against the batch's shape on the host
+    first -- an invalid row is refused here; the device would write that image as zeros.  ``out`` / ``scratch``: buffers to use."""
+    import torch
+    L = lib()
+    n, hs, ws, capacity = _resample_args(L, pixels, table)
+    if draw is not None:
+        if draw.units != n:
+            raise DyTError("resample: the draw holds %d images, the batch %d" % (draw.units, n))
+        try:
+            draw.check(hs, ws)
+        except ValueError as e:
+            raise DyTError(str(e))
+    pixels = pixels.contiguous()
+    if out is None:
+        out = torch.empty(n, 224, 224, 3, device=pixels.device, dtype=torch.uint8)
+    need = int(L.dyt_resample_scratch_bytes(n))
+    if scratch is None:
+        scratch = torch.empty(need // 4, device=pixels.device, dtype=torch.int32)
+    with torch.cuda.device(pixels.device):
+        check(L.dyt_resample_u8(ptr(pixels), n, hs, ws, ptr(out), ptr(table), capacity, ptr(scratch), scratch.numel() * scratch.element_size(),
+                                stream_ptr()), L)
+    return out
+
+
+def resample_coeffs(table, row, src_h, src_w):
+    """dyt_resample_coeffs: the coefficient tables the kernels compute for table row ``row`` of a batch padded to src_h x src_w -> int32
+    [2, 13, 224] on the device (axis 0 = output rows, 1 = columns; first tap, tap count, 11 coefficients per window position)."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_resample_coeffs"):
+        raise DyTError("this libdyt_hip has no dyt_resample_coeffs (device crop / resize): rebuild it")
+    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    out = torch.zeros(2, 13, 224, device=table.device, dtype=torch.int32)
+    with torch.cuda.device(table.device):
+        check(L.dyt_resample_coeffs(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
+    return out
+
+
 # csrc/eval_stats.h / DYT_EVAL_* of include/dyt_hip.h: the int64 `counts` state of the streaming evaluation
 EVAL_HEAD_WORDS, EVAL_ROWS, EVAL_IGNORED, EVAL_NAN_ROWS, EVAL_MASK_ROWS = 8, 0, 1, 2, 3
 EVAL_RANK_BINS, EVAL_OFF_RANK, EVAL_OFF_KEEP = 16, 8, 24
@@ -388,6 +448,9 @@ SYMBOLS = {
     "dyt_mix_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "dyt_set_erase": (_i, [_vp, _vp, _i, _i]),
     "dyt_erase_images": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp, _vp, _vp]),
+    "dyt_resample_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp]),
+    "dyt_resample_scratch_bytes": (_i64, [_i]),
+    "dyt_resample_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dyt_eval_rows": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dyt_eval_keep": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -440,7 +503,7 @@ SYMBOLS = {
 # Entries added without an ABI version change: discovered by their symbol.  A library of the same ABI version that lacks one (an older
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
-                    "dyt_set_erase", "dyt_erase_images",
+                    "dyt_set_erase", "dyt_erase_images", "dyt_resample_u8", "dyt_resample_scratch_bytes", "dyt_resample_coeffs",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
 
 _lib16 = None

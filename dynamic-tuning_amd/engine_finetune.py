@@ -19,6 +19,7 @@ import util.lr_sched as lr_sched
 from _lib import DyTError
 from util.mixup import DeviceMixup
 from util.erasing import DeviceRandomErasing
+from util.crop import DeviceRandomResizedCrop, DeviceResizeCenterCrop, full_sizes, probe_draw
 from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
@@ -626,6 +627,8 @@ class DevicePrefetcher:
         return len(self.loader)
 
     def _into(self, k, j, t):
+        if isinstance(t, (tuple, list)):   # (pixels, sizes) of a device-crop loader: the pixels travel, the sizes stay where the boxes are drawn
+            return (self._into(k, j, t[0]),) + tuple(t[1:])
         if not torch.is_tensor(t) or t.device == self.device:
             return t
         b = self.buf[k][j]
@@ -642,8 +645,14 @@ class DevicePrefetcher:
             self.copy_stream = self.pick_stream(None, None)   # a stream verified earlier (previous epoch): the first batch is prefetched too
         for it, batch in enumerate(self.loader):
             if self.copy_stream is None:   # the reference's placement: on the compute stream, in front of the step
-                xs, ys = batch[0].to(self.device, non_blocking=True), batch[1].to(self.device, non_blocking=True)
-                if self.on and not asked and xs is not batch[0]:
+                if isinstance(batch[0], (tuple, list)):   # (pixels, sizes): see _into
+                    xs = (batch[0][0].to(self.device, non_blocking=True),) + tuple(batch[0][1:])
+                    moved = xs[0] is not batch[0][0]
+                else:
+                    xs = batch[0].to(self.device, non_blocking=True)
+                    moved = xs is not batch[0]
+                ys = batch[1].to(self.device, non_blocking=True)
+                if self.on and not asked and moved:
                     asked = True
                     self.copy_stream = self.pick_stream(xs, ys)
                 yield it, xs, ys, tuple(batch[2:])
@@ -667,14 +676,17 @@ class DevicePrefetcher:
             self.free[k].record(torch.cuda.current_stream(self.device))
 
 
-def _copy_stream_picker(model, criterion, masked=None):
+def _copy_stream_picker(model, criterion, masked=None, cropper=None):
     """pick_stream of the training loop's DevicePrefetcher: the engine's verified copy stream, found once per engine by timing a
-    side-effect-free step (gradients into the engine's buffer, which the next real step overwrites; no optimizer update)."""
+    side-effect-free step (gradients into the engine's buffer, which the next real step overwrites; no optimizer update).  ``cropper``
+    (args.device_crop): the first batch is a source batch; the probe's step runs on a fixed crop of it that consumes no draw."""
     m = getattr(model, "module", model)
 
     def pick(samples, targets):
         if samples is None:   # only what is already known
             return getattr(getattr(m, "_engine", None), "_copy_stream_probe", (None, None))[0]
+        if cropper is not None:
+            samples = _resample_batch(m, cropper, samples, probe=True)
         x = m.prepare_input(samples)
         eng = m.engine(x.shape[0], x.device)
         if not hasattr(eng, "_copy_stream_probe"):
@@ -725,6 +737,38 @@ def _device_erasing(args, cube_default=False):
     return cached
 
 
+def _device_crop(args, name, kind, model, video=False):
+    """``args.device_crop`` (a util.crop.DeviceRandomResizedCrop) / ``args.device_eval_crop`` (a DeviceResizeCenterCrop), or None.  The
+    cropped batch is bytes, so the model must have been built with ``input_norm``; clips are refused."""
+    cropper = getattr(args, name, None) if args is not None else None
+    if cropper is None:
+        return None
+    if not isinstance(cropper, kind):
+        raise DyTError("args.%s must be a util.crop.%s (got %r)" % (name, kind.__name__, type(cropper)))
+    if video:
+        raise DyTError("args.%s: video clips are not implemented by the device crop (images only)" % name)
+    if getattr(model, "input_norm", None) is None:
+        raise DyTError("args.%s: the cropped batch is uint8, so the model must be built with input_norm (the mean / std the byte path "
+                       "normalises with)" % name)
+    return cropper
+
+
+def _resample_batch(model, cropper, samples, probe=False):
+    """A source batch -- ``(pixels uint8 [B, Hs, Ws, 3], sizes [B, 2] on the host)``, or a bare uint8 tensor [B, Hs, Ws, 3] that every
+    image fills -- on the device -> the 224 x 224 channels-last byte batch of the next draw, resampled on the current stream
+    (DyTEngine.resample).  ``probe``: a fixed draw that leaves the generators alone."""
+    pixels, sizes = (samples[0], samples[1]) if isinstance(samples, (tuple, list)) else (samples, None)
+    if not torch.is_tensor(pixels) or pixels.dim() == 5:
+        raise DyTError("device crop: video clips are not implemented (a source batch is uint8 [B, Hs, Ws, 3])")
+    if pixels.dtype != torch.uint8 or pixels.dim() != 4 or pixels.shape[3] != 3:
+        raise DyTError("device crop: a source batch is uint8 [B, Hs, Ws, 3], channels last (got %s %s)" % (pixels.dtype, tuple(pixels.shape)))
+    if sizes is None:
+        sizes = full_sizes(pixels)
+    eng = model.engine(pixels.shape[0], pixels.device)
+    draw = probe_draw(sizes) if probe else cropper.draw_for(sizes)
+    return eng.resample(pixels.contiguous(), sizes, draw)
+
+
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler=None, max_norm=0,
                     mixup_fn=None, log_writer=None, args=None, logger=None, _video=False):
     """Reference engine_finetune.py:16-106.  ``optimizer`` is the ``torch.optim.AdamW`` the drivers build (main_image.py:285;
@@ -734,9 +778,14 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     ``max_norm`` (--clip_grad) clips the global gradient norm on the device before the update.  ``args.hip_graph`` replays the
     step from a hipGraph.  ``args.random_erasing`` (a util.erasing.DeviceRandomErasing; or ``args.device_erase`` true, which builds one from
     ``args.reprob`` / ``args.remode`` / ``args.recount``, the names util/datasets.py reads): Random Erasing on the device, inside the fused
-    step's image load and before the mix of a DeviceMixup; with any other callable ``mixup_fn`` the batch is erased first (fp32 out)."""
+    step's image load and before the mix of a DeviceMixup; with any other callable ``mixup_fn`` the batch is erased first (fp32 out).
+    ``args.device_crop`` (a util.crop.DeviceRandomResizedCrop): the loader yields source batches -- ``((pixels uint8 [B, Hs, Ws, 3], sizes
+    [B, 2]), labels)`` as util.crop.pad_collate builds them, or bare uint8 [B, Hs, Ws, 3] tensors that every image fills -- and the loop
+    crops, resizes and flips them on the device into the 224 x 224 byte batch everything downstream (erasing, mixing, accum_iter,
+    hip_graph) sees as before.  The model must have ``input_norm``."""
     optimizer = as_fused(optimizer, model)
     eraser = _device_erasing(args, cube_default=_video)
+    cropper = _device_crop(args, "device_crop", DeviceRandomResizedCrop, getattr(model, "module", model), video=_video)
     if loss_scaler is not None and hasattr(loss_scaler, "bind"):
         loss_scaler.bind(optimizer)
     accum_iter = max(1, int(getattr(args, "accum_iter", 1) or 1)) if args is not None else 1
@@ -753,7 +802,9 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     t0 = time.time()
     lr = optimizer.param_groups[0]["lr"]
     # batch i+1 travels host -> device on a copy stream while step i runs (DevicePrefetcher); the reference's loop copies on the compute stream
-    for it, samples, targets, extra in DevicePrefetcher(data_loader, device, _copy_stream_picker(model, criterion)):
+    for it, samples, targets, extra in DevicePrefetcher(data_loader, device, _copy_stream_picker(model, criterion, cropper=cropper)):
+        if cropper is not None:   # the source batch becomes the 224 x 224 byte batch, on the compute stream, in front of the step
+            samples = _resample_batch(m, cropper, samples)
         # parity tests may append the random draws to inject: (samples, targets, (g1, g2), keep_mask)
         gumbel = tuple(t.to(device).contiguous() for t in extra[0]) if len(extra) > 0 and extra[0] is not None else None
         keep_mask = extra[1].to(device).contiguous() if len(extra) > 1 and extra[1] is not None else None
@@ -852,7 +903,10 @@ def _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_di
     the FLOPs table, ``gflops``."""
     model.eval()
     stats = None
+    cropper = _device_crop(args, "device_eval_crop", DeviceResizeCenterCrop, getattr(model, "module", model), video=video)
     for _, images, target, _ in DevicePrefetcher(data_loader, device, _verified_copy_stream(model)):
+        if cropper is not None:
+            images = _resample_batch(getattr(model, "module", model), cropper, images)
         if video:
             B, V = images.shape[0], images.shape[1]
             output, aux = model(images.flatten(0, 1))
@@ -884,12 +938,16 @@ def _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_di
 def evaluate(data_loader, model, device, logger=None, base_flops=None, flops_dict=None, args=None):
     """Reference engine_finetune.py:208-279: eval-mode forward over the loader, gather across ranks,
     top-1 (or mean-per-class) accuracy in ``status["metric"]``.  With ``args.stream_eval`` (or DYT_STREAM_EVAL=1) the statistics are folded into
-    a fixed-size device state batch by batch instead (``_evaluate_streaming``)."""
+    a fixed-size device state batch by batch instead (``_evaluate_streaming``).  ``args.device_eval_crop`` (a util.crop.DeviceResizeCenterCrop):
+    the loader yields source batches as for ``train_one_epoch``'s ``args.device_crop``; Resize + CenterCrop run on the device, both forms."""
     if stream_eval_requested(args):
         return _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_dict, args, video=False)
     model.eval()
     token_select, targets, predictions = [], [], []
+    cropper = _device_crop(args, "device_eval_crop", DeviceResizeCenterCrop, getattr(model, "module", model))
     for _, images, target, _ in DevicePrefetcher(data_loader, device, _verified_copy_stream(model)):
+        if cropper is not None:
+            images = _resample_batch(getattr(model, "module", model), cropper, images)
         output, aux = model(images)
         token_select.append(aux["token_select"].to(torch.uint8))  # {0,1}: 4x smaller gather than the reference's fp32
         predictions.append(output)

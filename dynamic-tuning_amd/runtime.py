@@ -671,6 +671,52 @@ class DyTEngine:
         params = None if mix is None else torch.frombuffer(bytearray(mix.words()), dtype=torch.int32).to(self.device)
         return erase_images(images, table, frames=self.frames, norm=self.input_norm, mix_params=params)
 
+    # ---- device crop / resize from byte sources ----------------------------------------------------
+    def resample(self, pixels, sizes, draw):
+        """dyt_resample_u8 on torch's current stream: the uint8 device batch ``pixels`` [B, Hs, Ws, 3] cropped, resized, windowed and mirrored
+        as ``draw`` (util.crop.CropDraw, e.g. ``DeviceRandomResizedCrop.draw_for(sizes)``) says -> uint8 [B, 224, 224, 3], the layout
+        DYT_F_IMAGES_U8 | DYT_F_IMAGES_NHWC reads.  ``sizes`` (host, [B, 2] = the images' valid height and width, or None): compared
+        with the draw's.  Like ``set_erase``: ONE static device table (a row for each of max_batch images), a small pinned host ring and a
+        non-blocking copy on the current stream -- the kernels read the table when they run, so a captured graph around them serves every
+        draw.  The scratch and output buffers are the engine's: the returned batch is valid until the next call."""
+        from _lib import resample_u8
+        from util.crop import table_words
+        if not hasattr(self.L, "dyt_resample_u8"):
+            raise DyTError("this libdyt_hip has no dyt_resample_u8 (device crop / resize): rebuild it")
+        n = int(pixels.shape[0])
+        cap = int(self.cfg.max_batch)
+        if draw.units != n:
+            raise DyTError("resample: the draw holds %d images, the batch %d" % (draw.units, n))
+        if n > cap:
+            raise DyTError("resample: the batch has %d images, the engine's max_batch is %d" % (n, cap))
+        if sizes is not None:
+            given = [tuple(int(v) for v in r) for r in (sizes.tolist() if hasattr(sizes, "tolist") else sizes)]
+            if given != [(r[0], r[1]) for r in draw.rows]:
+                raise DyTError("resample: the draw was made for other image sizes than the batch's")
+        try:
+            draw.check(int(pixels.shape[1]), int(pixels.shape[2]))   # an invalid row is refused before upload (the device would write zeros)
+        except ValueError as e:
+            raise DyTError(str(e))
+        words = draw.words(cap)
+        if getattr(self, "_rs_dev", None) is None:
+            self._rs_dev = torch.zeros(table_words(cap), dtype=torch.int32, device=self.device)
+            self._rs_ring = torch.zeros(self.MIX_RING, table_words(cap), dtype=torch.int32).pin_memory()
+            self._rs_events = [None] * self.MIX_RING
+            self._rs_at = 0
+            self._rs_out = torch.empty(cap, 224, 224, 3, dtype=torch.uint8, device=self.device)
+            self._rs_scratch = torch.empty(int(self.L.dyt_resample_scratch_bytes(cap)) // 4, dtype=torch.int32, device=self.device)
+        k = self._rs_at
+        self._rs_at = (k + 1) % self.MIX_RING
+        if self._rs_events[k] is not None:
+            self._rs_events[k].synchronize()   # the copy that read this slot MIX_RING draws ago: long complete, this does not wait
+        self._rs_ring[k].copy_(torch.frombuffer(bytearray(words), dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            self._rs_dev.copy_(self._rs_ring[k], non_blocking=True)
+            if self._rs_events[k] is None:
+                self._rs_events[k] = torch.cuda.Event()
+            self._rs_events[k].record()
+        return resample_u8(pixels, self._rs_dev, None, out=self._rs_out[:n], scratch=self._rs_scratch)
+
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on):
         self._ck(self.L.dyt_profile_enable(self.h, 1 if on else 0))

@@ -1,0 +1,258 @@
+"""RandomResizedCrop + RandomHorizontalFlip / Resize + CenterCrop on the device, from byte sources: ``DeviceRandomResizedCrop`` stands where
+``util/crop.py``'s ``RandomResizedCrop(224, interpolation=3)`` followed by ``RandomHorizontalFlip()`` stands in the reference's train
+pipeline (datasets/image_datasets.py), ``DeviceResizeCenterCrop`` where ``Resize(256, interpolation=3)`` + ``CenterCrop(224)`` stand in its
+evaluation pipeline.  The loader decodes and pads only (``pad_collate``); the boxes are drawn on the host and the pixels are written on the
+device (csrc/resample.h, csrc/resample.hip): Pillow's 8-bit bicubic ``Image.resize`` restated bit for bit.
+
+The draws are a RESTATEMENT of the reference ``RandomResizedCrop.get_params`` (torchvision is not a dependency), per image in this order:
+
+    1. ``torch.empty(1).uniform_(scale[0], scale[1])`` for the area, as a fraction of the image's
+    2. ``torch.empty(1).uniform_(log ratio[0], log ratio[1])`` for the log aspect ratio (the logs and the ``exp`` in fp32, as there);
+       w and h rounded and clipped to the image
+    3. ``torch.randint(0, height - h + 1, (1,))`` for the top and ``torch.randint(0, width - w + 1, (1,))`` for the left edge
+    4. ``torch.rand(1) < flip``: RandomHorizontalFlip's own call (``flip=None``: no flip stage, no draw)
+
+With ``generator=None`` they come from torch's global generator, as the reference's do, so a seeded run draws the reference's boxes.
+
+Two ways to use it:
+  * ``train_one_epoch(..., args)`` with ``args.device_crop = DeviceRandomResizedCrop()`` (``evaluate`` with
+    ``args.device_eval_crop = DeviceResizeCenterCrop()``): the loader yields ``((pixels, sizes), labels)``, the loop draws, the engine
+    resamples on the compute stream (``DyTEngine.resample``) and the step sees a 224 x 224 channels-last byte batch.
+  * ``cropped = DeviceRandomResizedCrop()(pixels, sizes)`` on a device batch: uint8 [B, 224, 224, 3] out (libdyt_hip's dyt_resample_u8).
+"""
+import math
+import struct
+
+OUT = 224
+BICUBIC = 3
+HEADER_WORDS, ROW_WORDS = 16, 12
+MAX_SIDE = 4096
+FLAG_MIRROR = 1
+
+
+def table_words(capacity):
+    """32-bit words of a table with ``capacity`` rows (csrc/resample.h)."""
+    return HEADER_WORDS + ROW_WORDS * int(capacity)
+
+
+def row_error(row, batch_h=None, batch_w=None):
+    """csrc/resample.h's resample_row_ok as a text (None: the row is valid)."""
+    sh, sw, top, left, bh, bw, fh, fw, oy, ox, flags = row
+    if sh < 1 or sw < 1:
+        return "the valid extent %d x %d is empty" % (sh, sw)
+    if (batch_h is not None and sh > batch_h) or (batch_w is not None and sw > batch_w):
+        return "the valid extent %d x %d lies outside the batch's %s x %s" % (sh, sw, batch_h, batch_w)
+    if bh < 1 or bw < 1:
+        return "the box has h < 1 or w < 1 (%d x %d)" % (bh, bw)
+    if top < 0 or left < 0 or top + bh > sh or left + bw > sw:
+        return "the box (top %d, left %d, %d x %d) lies outside the image's %d x %d" % (top, left, bh, bw, sh, sw)
+    if fh < OUT or fw < OUT:
+        return "the resized image %d x %d is smaller than the %d x %d window" % (fh, fw, OUT, OUT)
+    if oy < 0 or ox < 0 or oy + OUT > fh or ox + OUT > fw:
+        return "the window (offset %d, %d) lies outside the resized image %d x %d" % (oy, ox, fh, fw)
+    if 2 * bh > 5 * fh or 2 * bw > 5 * fw:
+        return ("the box %d x %d is more than 2.5 times the resized image %d x %d (the kernels take at most 11 taps): decode to a smaller "
+                "size" % (bh, bw, fh, fw))
+    return None
+
+
+class CropDraw:
+    """The host-side parameters of one batch: per image the row ``(src_h, src_w, top, left, box_h, box_w, full_h, full_w, off_y, off_x,
+    flags)`` of csrc/resample.h.  ``words(capacity)`` is the table the kernels read."""
+
+    def __init__(self, rows):
+        self.rows = [tuple(int(v) for v in r) for r in rows]
+        if not self.rows:
+            raise ValueError("resample: the draw holds no image")
+        for r in self.rows:
+            if len(r) != 11:
+                raise ValueError("resample: a row is (src_h, src_w, top, left, box_h, box_w, full_h, full_w, off_y, off_x, flags), got %r" % (r,))
+        self.check()
+
+    @property
+    def units(self):
+        return len(self.rows)
+
+    def images(self):
+        return len(self.rows)
+
+    def check(self, batch_h=None, batch_w=None):
+        """The refusal of an invalid row, made where the values are still on the host (the device would write such an image as zeros)."""
+        for i, r in enumerate(self.rows):
+            e = row_error(r, batch_h, batch_w)
+            if e:
+                raise ValueError("resample: image %d: %s" % (i, e))
+
+    def boxes(self):
+        """[(i, j, h, w)] as ``get_params`` returns them."""
+        return [(r[2], r[3], r[4], r[5]) for r in self.rows]
+
+    def flips(self):
+        return [bool(r[10] & FLAG_MIRROR) for r in self.rows]
+
+    def words(self, capacity=None):
+        """The table as bytes: the 16-word header, the rows of this draw, zero rows up to ``capacity``."""
+        capacity = self.units if capacity is None else int(capacity)
+        if capacity < self.units:
+            raise ValueError("resample: the draw holds %d images, the table %d" % (self.units, capacity))
+        out = [struct.pack("<16i", BICUBIC, self.units, *([0] * 14))]
+        for r in self.rows:
+            out.append(struct.pack("<12i", *r, 0))
+        out.append(b"\0" * (4 * ROW_WORDS * (capacity - self.units)))
+        return b"".join(out)
+
+    def __repr__(self):
+        return "CropDraw(%r)" % (self.rows,)
+
+
+def _sizes_list(sizes):
+    """[(h, w)] from an int tensor / array / list [B, 2] that lives on the host."""
+    if hasattr(sizes, "is_cuda") and sizes.is_cuda:
+        raise ValueError("resample: sizes must stay on the host (the boxes are drawn there)")
+    rows = sizes.tolist() if hasattr(sizes, "tolist") else list(sizes)
+    out = []
+    for r in rows:
+        if len(r) != 2:
+            raise ValueError("resample: sizes is [B, 2] = (height, width) per image, got a row %r" % (r,))
+        h, w = int(r[0]), int(r[1])
+        if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
+            raise ValueError("resample: an image of %d x %d (sides are 1 to %d)" % (h, w, MAX_SIDE))
+        out.append((h, w))
+    if not out:
+        raise ValueError("resample: sizes holds no image")
+    return out
+
+
+def full_sizes(pixels):
+    """The sizes of a bare batch [B, Hs, Ws, 3] that every image fills."""
+    return [(int(pixels.shape[1]), int(pixels.shape[2]))] * int(pixels.shape[0])
+
+
+class _DeviceCrop:
+    def __call__(self, pixels, sizes=None):
+        """The cropped byte batch uint8 [B, 224, 224, 3] of a device batch uint8 [B, Hs, Ws, 3]; ``sizes`` [B, 2] (host) = the images' valid
+        (height, width), None: every image fills the batch's shape."""
+        from _lib import resample_u8
+        import torch
+        d = self.draw_for(full_sizes(pixels) if sizes is None else sizes)
+        if d.units != int(pixels.shape[0]):
+            raise ValueError("resample: %d sizes for a batch of %d images" % (d.units, int(pixels.shape[0])))
+        table = torch.frombuffer(bytearray(d.words()), dtype=torch.int32).to(pixels.device)
+        return resample_u8(pixels, table, d)
+
+
+class DeviceRandomResizedCrop(_DeviceCrop):
+    """The reference RandomResizedCrop's arguments plus ``flip`` (RandomHorizontalFlip's p; None: no flip stage) and ``generator`` (a
+    torch.Generator; None: torch's global one, as the reference).  Only what the kernels implement is accepted: size 224, bicubic."""
+
+    def __init__(self, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation=3, flip=0.5, generator=None):
+        if isinstance(size, (tuple, list)):
+            size = size[0] if len(size) == 1 or (len(size) == 2 and size[0] == size[1]) else size
+        if size != OUT:
+            raise NotImplementedError("DeviceRandomResizedCrop: size=%r is not implemented (the kernels write 224 x 224)" % (size,))
+        if getattr(interpolation, "value", interpolation) not in (BICUBIC, "bicubic"):
+            raise NotImplementedError("DeviceRandomResizedCrop: interpolation=%r is not implemented (3 = bicubic only)" % (interpolation,))
+        if len(scale) != 2 or len(ratio) != 2 or not (0 < scale[0] <= scale[1]) or not (0 < ratio[0] <= ratio[1]):
+            raise ValueError("DeviceRandomResizedCrop: scale and ratio are (min, max) with 0 < min <= max")
+        if flip is not None and not (0.0 <= float(flip) <= 1.0):
+            raise ValueError("DeviceRandomResizedCrop: flip is a probability or None")
+        self.size, self.scale, self.ratio, self.interpolation, self.flip, self.generator = OUT, tuple(scale), tuple(ratio), BICUBIC, flip, generator
+        self._injected = []
+
+    def inject(self, draws):
+        """Fixed draws (CropDraw objects) that the next calls of ``draw_for()`` hand out in order: for tests and recorded runs."""
+        self._injected.extend(draws)
+        return self
+
+    def get_params(self, height, width):
+        """(i, j, h, w) of one image: the reference's ``get_params`` line by line.  A side that rounds to 0 (images of a few pixels) is
+        raised to 1, where the reference would crop an empty box."""
+        import torch
+        g = self.generator
+        area = height * width
+        target_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1], generator=g).item()
+        log_ratio = torch.log(torch.tensor(self.ratio))
+        aspect_ratio = torch.exp(torch.empty(1).uniform_(float(log_ratio[0]), float(log_ratio[1]), generator=g)).item()
+        w = int(round(math.sqrt(target_area * aspect_ratio)))
+        h = int(round(math.sqrt(target_area / aspect_ratio)))
+        w = max(1, min(w, width))
+        h = max(1, min(h, height))
+        i = torch.randint(0, height - h + 1, size=(1,), generator=g).item()
+        j = torch.randint(0, width - w + 1, size=(1,), generator=g).item()
+        return i, j, h, w
+
+    def draw_for(self, sizes):
+        """The draw of a batch whose images have the (height, width) rows of ``sizes``."""
+        import torch
+        sizes = _sizes_list(sizes)
+        if self._injected:
+            d = self._injected.pop(0)
+            if d.units != len(sizes):
+                raise ValueError("resample: the injected draw holds %d images, the batch %d" % (d.units, len(sizes)))
+            return d
+        rows = []
+        for (sh, sw) in sizes:
+            i, j, h, w = self.get_params(sh, sw)
+            mirror = bool(torch.rand(1, generator=self.generator) < self.flip) if self.flip is not None else False
+            rows.append((sh, sw, i, j, h, w, OUT, OUT, 0, 0, FLAG_MIRROR if mirror else 0))
+        return CropDraw(rows)
+
+
+class DeviceResizeCenterCrop(_DeviceCrop):
+    """``Resize(resize, interpolation=3)`` + ``CenterCrop(size)`` of torchvision: the short side becomes ``resize``, the long side
+    ``int(resize * long / short)``; the window starts at ``int(round((full - size) / 2.0))``.  Makes no draw."""
+
+    def __init__(self, resize=256, size=224, interpolation=3):
+        if size != OUT:
+            raise NotImplementedError("DeviceResizeCenterCrop: size=%r is not implemented (the kernels write 224 x 224)" % (size,))
+        if getattr(interpolation, "value", interpolation) not in (BICUBIC, "bicubic"):
+            raise NotImplementedError("DeviceResizeCenterCrop: interpolation=%r is not implemented (3 = bicubic only)" % (interpolation,))
+        if int(resize) != resize or resize < OUT:
+            raise ValueError("DeviceResizeCenterCrop: resize is an integer >= %d (the window must fit), got %r" % (OUT, resize))
+        self.resize, self.size = int(resize), OUT
+
+    def geometry(self, height, width):
+        """(full_h, full_w, off_y, off_x)"""
+        if width <= height:
+            fw, fh = self.resize, int(self.resize * height / width)
+        else:
+            fh, fw = self.resize, int(self.resize * width / height)
+        return fh, fw, int(round((fh - OUT) / 2.0)), int(round((fw - OUT) / 2.0))
+
+    def draw_for(self, sizes):
+        rows = []
+        for (sh, sw) in _sizes_list(sizes):
+            fh, fw, oy, ox = self.geometry(sh, sw)
+            rows.append((sh, sw, 0, 0, sh, sw, fh, fw, oy, ox, 0))
+        return CropDraw(rows)
+
+
+def probe_draw(sizes):
+    """A valid draw that consumes no random number (the top-left 224 x 224 of every image, or the whole of a smaller one): for the loop's
+    one-off stream probe, which needs a batch of the step's shape and must leave the generators alone."""
+    return CropDraw([(sh, sw, 0, 0, min(sh, OUT), min(sw, OUT), OUT, OUT, 0, 0, 0) for (sh, sw) in _sizes_list(sizes)])
+
+
+def pad_collate(batch, pad_to=None):
+    """collate_fn of a loader that decodes only: a list of ``(image, label)`` with ``image`` an HWC uint8 array / tensor [h, w, 3] ->
+    ``((pixels uint8 [B, Hs, Ws, 3], sizes int32 [B, 2]), labels int64 [B])``.  Hs, Ws = the largest height and width of the batch (or
+    ``pad_to`` = (Hs, Ws), which keeps the shape the same from batch to batch); the padding is zeros and never reaches an output."""
+    import numpy as np
+    import torch
+    images = [np.asarray(b[0]) for b in batch]
+    for im in images:
+        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+            raise ValueError("pad_collate takes HWC uint8 images [h, w, 3] (got %s %s)" % (im.dtype, im.shape))
+        if im.shape[0] < 1 or im.shape[1] < 1 or im.shape[0] > MAX_SIDE or im.shape[1] > MAX_SIDE:
+            raise ValueError("pad_collate: an image of %d x %d (sides are 1 to %d)" % (im.shape[0], im.shape[1], MAX_SIDE))
+    hs, ws = max(im.shape[0] for im in images), max(im.shape[1] for im in images)
+    if pad_to is not None:
+        if pad_to[0] < hs or pad_to[1] < ws:
+            raise ValueError("pad_collate: pad_to=%r is smaller than an image of the batch (%d x %d)" % (tuple(pad_to), hs, ws))
+        hs, ws = int(pad_to[0]), int(pad_to[1])
+    pixels = torch.zeros(len(images), hs, ws, 3, dtype=torch.uint8)
+    for i, im in enumerate(images):
+        pixels[i, :im.shape[0], :im.shape[1]] = torch.from_numpy(np.ascontiguousarray(im))
+    sizes = torch.tensor([[im.shape[0], im.shape[1]] for im in images], dtype=torch.int32)
+    labels = torch.as_tensor([int(b[1]) for b in batch], dtype=torch.int64)
+    return (pixels, sizes), labels

@@ -430,6 +430,30 @@ int dyt_set_erase(dyt_ctx* ctx, const void* table_dev, int units_capacity, int f
  * erased mirror (count an even number of clips).  One launch on `stream`. */
 int dyt_erase_images(const void* src, float* dst, int count, int frames, int src_kind, const float mean[3], const float std[3], const void* table_dev, const void* mix_params_dev, void* stream);
 
+/* Device RandomResizedCrop + horizontal flip / Resize + CenterCrop from byte sources (csrc/resample.h, csrc/resample.hip): Pillow's bicubic
+ * Image.resize for 8-bit images restated bit for bit -- fp64 coefficients quantised to 22 bits, an int32 horizontal pass that rounds to
+ * uint8, an int32 vertical pass on those bytes -- applied to a crop box that acts as the image (crop, then resize).  Three context-free
+ * entries, added without an ABI version change (the version stays 5) and discovered by their symbols; the same bits from both libraries.
+ * src uint8 [batch, src_h, src_w, 3] (channels-last, padded to one shape) -> dst uint8 [batch, 224, 224, 3], the layout
+ * DYT_F_IMAGES_U8 | DYT_F_IMAGES_NHWC reads.  The draw lives in DEVICE memory: table_dev points to 32-bit words, 16-byte aligned --
+ *   16 header words: filter (3 = bicubic; any other value: every image is written as zeros), units (rows in use), 14 reserved words;
+ *   then one row of 12 words per image: src_h, src_w (the image's valid extent inside the padded shape), top, left, box_h, box_w (the crop
+ *   box), full_h, full_w (the size the box is resized to), off_y, off_x (the 224 x 224 window inside it), flags (bit 0: mirror the output
+ *   columns), one unused word
+ * -- and is read by the kernels when they RUN: a captured graph replayed after the table was overwritten resamples with the new draw.
+ * A row is valid when the box lies inside the valid extent, the extent inside [src_h, src_w], 1 <= box, 224 <= full, the window inside
+ * full, and box <= 2.5 full per axis (at most 11 taps).  Nothing of a row is used as an index before that check (64-bit comparisons); an
+ * image whose row fails it, or that has no row (image number >= units), is written as ZEROS.  capacity = the rows the allocation behind
+ * table_dev holds.  scratch_dev: dyt_resample_scratch_bytes(batch) bytes at least, 16-byte aligned (the coefficient tables: 23 296 bytes
+ * per image).  Two launches on `stream`.  Refused with a text, before anything is enqueued: null or misaligned pointers, batch < 1,
+ * batch > capacity, a scratch buffer that is too small, a source side < 1 or above 4096. */
+int dyt_resample_u8(const uint8_t* src, int batch, int src_h, int src_w, uint8_t* dst, const void* table_dev, int capacity, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int64_t dyt_resample_scratch_bytes(int batch);
+/* Debug / test entry: the coefficient tables of table row `row` as the kernels compute them -> out_dev int32 [2][13][224] (16-byte aligned):
+ * axis 0 = output rows, 1 = output columns; per axis the first tap (relative to the box), the tap count and 11 coefficients of each of
+ * the 224 window positions.  An invalid row gives zeros.  One launch on `stream`. */
+int dyt_resample_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream);
+
 /* Streaming evaluation statistics (csrc/eval_stats.h, csrc/eval_stats.hip): a batch of logits, labels and token masks is folded into a
  * fixed-size device-resident state, so that an evaluation loop keeps no per-sample tensor.  Two context-free entries, added without an ABI
  * version change (the version stays 5) and discovered by their symbols; pure fp32 / integer, the same bits from both libraries.
