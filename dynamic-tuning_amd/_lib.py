@@ -360,6 +360,67 @@ def resample_coeffs(table, row, src_h, src_w):
     return out
 
 
+RESAMPLE_BILINEAR_F32, RESAMPLE_CLIP_COEFF_WORDS = 2, 2 * 4 * 224   # csrc/resample_clip.h
+IMAGENET_NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
+
+
+def resample_clip_f32(clips, table, draw=None, out=None, norm=None, units=None):
+    """dyt_resample_clip_f32: a uint8 device batch of clips [B, T, Hs, Ws, 3] (as a decoder yields them, padded) normalised with ``norm``
+    = (mean, std) (None: the ImageNet statistics), resized with torch's float bilinear arithmetic, windowed and mirrored as the clip rows
+    of the device table ``table`` say (util.crop.CropDraw(rows, filter=2).words()): output unit r is written from row r, which reads
+    source clip ``src`` -> fp32, returned as the [units, 3, T, 224, 224] permuted view of the kernel's contiguous [units, T, 3, 224, 224],
+    on torch's current stream.  ``draw`` (the CropDraw behind the table): checked against the batch's shape on the host first -- an
+    invalid row is refused here; the device would write that unit as zeros.  ``out``: a contiguous fp32 buffer [units, T, 3, 224, 224]."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_resample_clip_f32"):
+        raise DyTError("this libdyt_hip has no dyt_resample_clip_f32 (device clip pipeline): rebuild it")
+    if not (torch.is_tensor(clips) and clips.is_cuda and clips.dtype == torch.uint8 and clips.dim() == 5 and clips.shape[4] == 3):
+        raise DyTError("resample clip takes a uint8 device batch of clips [B, T, Hs, Ws, 3] (got %s %s); images go through resample_u8" % (
+            getattr(clips, "dtype", type(clips)), tuple(getattr(clips, "shape", ()))))
+    n, t, hs, ws = (int(v) for v in clips.shape[:4])
+    if n < 1 or t < 1 or hs < 1 or ws < 1 or hs > RESAMPLE_MAX_SIDE or ws > RESAMPLE_MAX_SIDE:
+        raise DyTError("resample clip: a batch of %d clips of %d frames of %d x %d (at least one, sides 1 to %d)" % (n, t, hs, ws, RESAMPLE_MAX_SIDE))
+    if draw is not None:
+        if not getattr(draw, "clip", False):
+            raise DyTError("resample clip: the draw holds image rows (a CropDraw with filter=2 holds clip rows)")
+        if units is not None and int(units) != draw.units:
+            raise DyTError("resample clip: the draw holds %d rows, %d units were asked for" % (draw.units, int(units)))
+        units = draw.units
+        try:
+            draw.check(hs, ws, n)
+        except ValueError as e:
+            raise DyTError(str(e))
+    units = n if units is None else int(units)
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and units >= 1 and
+            table.numel() >= RESAMPLE_HEADER_WORDS + RESAMPLE_ROW_WORDS * units):
+        raise DyTError("resample clip table: a contiguous int32 device tensor of 16 + 12 x %d words at least (util.crop.CropDraw.words(capacity))" % units)
+    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    clips = clips.contiguous()
+    if out is None:
+        out = torch.empty(units, t, 3, 224, 224, device=clips.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (units, t, 3, 224, 224)):
+        raise DyTError("resample clip: out is a contiguous fp32 device tensor [%d, %d, 3, 224, 224]" % (units, t))
+    mean, std = IMAGENET_NORM if norm is None else norm
+    with torch.cuda.device(clips.device):
+        check(L.dyt_resample_clip_f32(ptr(clips), n, t, hs, ws, ptr(out), units, ptr(table), capacity, float3(mean), float3(std), stream_ptr()), L)
+    return out.permute(0, 2, 1, 3, 4)
+
+
+def resample_clip_coeffs(table, row, src_h, src_w):
+    """dyt_resample_clip_coeffs: the taps and weights the kernel computes for clip row ``row`` of a batch padded to src_h x src_w -> int32
+    [2, 4, 224] on the device (axis 0 = output rows, 1 = columns; i0, i1 relative to the box, the bit patterns of l0 and l1)."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_resample_clip_coeffs"):
+        raise DyTError("this libdyt_hip has no dyt_resample_clip_coeffs (device clip pipeline): rebuild it")
+    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    out = torch.zeros(2, 4, 224, device=table.device, dtype=torch.int32)
+    with torch.cuda.device(table.device):
+        check(L.dyt_resample_clip_coeffs(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
+    return out
+
+
 # csrc/eval_stats.h / DYT_EVAL_* of include/dyt_hip.h: the int64 `counts` state of the streaming evaluation
 EVAL_HEAD_WORDS, EVAL_ROWS, EVAL_IGNORED, EVAL_NAN_ROWS, EVAL_MASK_ROWS = 8, 0, 1, 2, 3
 EVAL_RANK_BINS, EVAL_OFF_RANK, EVAL_OFF_KEEP = 16, 8, 24
@@ -451,6 +512,8 @@ SYMBOLS = {
     "dyt_resample_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp]),
     "dyt_resample_scratch_bytes": (_i64, [_i]),
     "dyt_resample_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "dyt_resample_clip_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp]),
+    "dyt_resample_clip_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dyt_eval_rows": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dyt_eval_keep": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -504,6 +567,7 @@ SYMBOLS = {
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
                     "dyt_set_erase", "dyt_erase_images", "dyt_resample_u8", "dyt_resample_scratch_bytes", "dyt_resample_coeffs",
+                    "dyt_resample_clip_f32", "dyt_resample_clip_coeffs",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
 
 _lib16 = None

@@ -59,7 +59,7 @@ static int pool_backward(dyt_ctx* c, Slot& S, const float* tr, const float* dlog
     RUN(2, 0, launch_transpose_rows(P, Q.xv, Q.xvt, M, Mp, nullptr, s));
     RUN(2, 0, launch_reduce_partials(T.tok_partial, Mp / 64, D, grad + c->off_pv_bias, D, inv_gs, s));
     hipStream_t ws = nullptr;
-    if (c->overlap && !c->prof) {
+    if (c->overlap && !c->prof && !S.no_branch) {   // (no_branch: a captured teacher pass -- a fork of the side stream crashes hipStreamEndCapture, see dyt_step_fwd_bwd)
         if (!Q.wstream) {
             DYT_HIP_CHECK(hipStreamCreateWithFlags(&Q.wstream, hipStreamNonBlocking));
             DYT_HIP_CHECK(hipEventCreateWithFlags(&Q.ev_wf, hipEventDisableTiming));

@@ -19,7 +19,8 @@ import util.lr_sched as lr_sched
 from _lib import DyTError
 from util.mixup import DeviceMixup
 from util.erasing import DeviceRandomErasing
-from util.crop import DeviceRandomResizedCrop, DeviceResizeCenterCrop, full_sizes, probe_draw
+from util.crop import (DeviceClipRandomResizedCrop, DeviceClipScaleJitterCrop, DeviceClipUniformCrop, DeviceRandomResizedCrop,
+                       DeviceResizeCenterCrop, _DeviceClipCrop, full_clip_sizes, full_sizes, probe_clip_draw, probe_draw)
 from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
@@ -738,17 +739,27 @@ def _device_erasing(args, cube_default=False):
 
 
 def _device_crop(args, name, kind, model, video=False):
-    """``args.device_crop`` (a util.crop.DeviceRandomResizedCrop) / ``args.device_eval_crop`` (a DeviceResizeCenterCrop), or None.  The
-    cropped batch is bytes, so the model must have been built with ``input_norm``; clips are refused."""
+    """``args.device_crop`` / ``args.device_eval_crop``, or None.  Images: a util.crop.DeviceRandomResizedCrop / DeviceResizeCenterCrop
+    (``kind``); the cropped batch is bytes.  Video (``video``): a DeviceClipScaleJitterCrop or DeviceClipRandomResizedCrop /
+    a DeviceClipUniformCrop; the cropped batch is the normalised float clip.  Either way the model must have been built with ``input_norm``;
+    an image class on a clip loop and a clip class on an image loop are refused."""
     cropper = getattr(args, name, None) if args is not None else None
     if cropper is None:
         return None
-    if not isinstance(cropper, kind):
-        raise DyTError("args.%s must be a util.crop.%s (got %r)" % (name, kind.__name__, type(cropper)))
+    clip_kinds = (DeviceClipUniformCrop,) if name == "device_eval_crop" else (DeviceClipScaleJitterCrop, DeviceClipRandomResizedCrop)
     if video:
-        raise DyTError("args.%s: video clips are not implemented by the device crop (images only)" % name)
+        if isinstance(cropper, (DeviceRandomResizedCrop, DeviceResizeCenterCrop)):
+            raise DyTError("args.%s: video clips are not implemented by util.crop.%s (images only); a clip loop takes util.crop.%s" % (
+                name, type(cropper).__name__, " / ".join(k.__name__ for k in clip_kinds)))
+        if not isinstance(cropper, clip_kinds):
+            raise DyTError("args.%s of a clip loop must be a util.crop.%s (got %r)" % (name, " / ".join(k.__name__ for k in clip_kinds), type(cropper)))
+    else:
+        if isinstance(cropper, _DeviceClipCrop):
+            raise DyTError("args.%s: util.crop.%s crops video clips; an image loop takes a util.crop.%s" % (name, type(cropper).__name__, kind.__name__))
+        if not isinstance(cropper, kind):
+            raise DyTError("args.%s must be a util.crop.%s (got %r)" % (name, kind.__name__, type(cropper)))
     if getattr(model, "input_norm", None) is None:
-        raise DyTError("args.%s: the cropped batch is uint8, so the model must be built with input_norm (the mean / std the byte path "
+        raise DyTError("args.%s: the source batch is uint8, so the model must be built with input_norm (the mean / std the byte path "
                        "normalises with)" % name)
     return cropper
 
@@ -756,10 +767,12 @@ def _device_crop(args, name, kind, model, video=False):
 def _resample_batch(model, cropper, samples, probe=False):
     """A source batch -- ``(pixels uint8 [B, Hs, Ws, 3], sizes [B, 2] on the host)``, or a bare uint8 tensor [B, Hs, Ws, 3] that every
     image fills -- on the device -> the 224 x 224 channels-last byte batch of the next draw, resampled on the current stream
-    (DyTEngine.resample).  ``probe``: a fixed draw that leaves the generators alone."""
+    (DyTEngine.resample).  ``probe``: a fixed draw that leaves the generators alone.  With a clip class: ``_resample_clip_batch``."""
+    if isinstance(cropper, _DeviceClipCrop):
+        return _resample_clip_batch(model, cropper, samples, probe=probe)
     pixels, sizes = (samples[0], samples[1]) if isinstance(samples, (tuple, list)) else (samples, None)
     if not torch.is_tensor(pixels) or pixels.dim() == 5:
-        raise DyTError("device crop: video clips are not implemented (a source batch is uint8 [B, Hs, Ws, 3])")
+        raise DyTError("device crop: video clips are not implemented by the image classes (a source batch is uint8 [B, Hs, Ws, 3])")
     if pixels.dtype != torch.uint8 or pixels.dim() != 4 or pixels.shape[3] != 3:
         raise DyTError("device crop: a source batch is uint8 [B, Hs, Ws, 3], channels last (got %s %s)" % (pixels.dtype, tuple(pixels.shape)))
     if sizes is None:
@@ -767,6 +780,45 @@ def _resample_batch(model, cropper, samples, probe=False):
     eng = model.engine(pixels.shape[0], pixels.device)
     draw = probe_draw(sizes) if probe else cropper.draw_for(sizes)
     return eng.resample(pixels.contiguous(), sizes, draw)
+
+
+def _resample_clip_batch(model, cropper, samples, probe=False):
+    """A source batch of clips -- ``(clips uint8 [B, T, Hs, Ws, 3], sizes [B, 2] on the host)`` as util.crop.pad_collate_clips builds it, or
+    a bare uint8 tensor that every clip fills -- on the device -> the normalised, resized, windowed and mirrored float clips of the next
+    draw, on the current stream (DyTEngine.resample_clip).  A training class gives [B, 3, T, 224, 224].  A DeviceClipUniformCrop
+    (evaluation) also takes [B, Vt, T, Hs, Ws, 3] -- temporal views decoded by the loader -- and gives [B, Vt * S, 3, T, 224, 224],
+    temporal-major, as the reference's ``sum([spatial_crops(clip) for clip in clips], [])`` orders them.  The result is a view of the
+    engine's buffer that the video model folds without a copy."""
+    clips, sizes = (samples[0], samples[1]) if isinstance(samples, (tuple, list)) else (samples, None)
+    evaluation = isinstance(cropper, DeviceClipUniformCrop)
+    if not torch.is_tensor(clips) or clips.dim() not in ((5, 6) if evaluation else (5,)):
+        raise DyTError("device clip crop: a source batch is uint8 [B, T, Hs, Ws, 3]%s; image batches go through the image classes (got %s)" % (
+            " or [B, Vt, T, Hs, Ws, 3]" if evaluation else "", tuple(clips.shape) if torch.is_tensor(clips) else type(clips)))
+    if clips.dtype != torch.uint8 or clips.shape[-1] != 3:
+        raise DyTError("device clip crop: a source batch is uint8 [B, T, Hs, Ws, 3], channels last (got %s %s)" % (clips.dtype, tuple(clips.shape)))
+    if getattr(model, "_frames", 1) == 1:
+        raise DyTError("device clip crop: the model is an image model (clips need video_models.video_vision_transformer_IN21K)")
+    batch, tviews = int(clips.shape[0]), 1
+    if clips.dim() == 6:
+        tviews = int(clips.shape[1])
+        clips = clips.flatten(0, 1)
+    if sizes is None:
+        sizes = full_clip_sizes(clips)
+    else:
+        sizes = [tuple(int(v) for v in r) for r in (sizes.tolist() if hasattr(sizes, "tolist") else sizes)]
+        if len(sizes) != batch:
+            raise DyTError("device clip crop: %d sizes for a batch of %d clips" % (len(sizes), batch))
+        sizes = [s for s in sizes for _ in range(tviews)]
+    frames = int(clips.shape[1])
+    if frames < 2:
+        raise DyTError("the video model needs t >= 2 frames per clip; use models.vision_transformer_IN21K for images")
+    if model._frames is not None and frames != model._frames and model._engine is not None:
+        model._engine = None   # frames per clip changed: the library context is rebuilt (as fold_input does)
+    model._frames = frames
+    draw = probe_clip_draw(sizes) if probe else cropper.draw_for(sizes)
+    eng = model.engine(draw.units * frames, clips.device)
+    out = eng.resample_clip(clips.contiguous(), sizes, draw)
+    return out.unflatten(0, (batch, tviews * cropper.views)) if evaluation else out
 
 
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler=None, max_norm=0,
@@ -782,7 +834,11 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     ``args.device_crop`` (a util.crop.DeviceRandomResizedCrop): the loader yields source batches -- ``((pixels uint8 [B, Hs, Ws, 3], sizes
     [B, 2]), labels)`` as util.crop.pad_collate builds them, or bare uint8 [B, Hs, Ws, 3] tensors that every image fills -- and the loop
     crops, resizes and flips them on the device into the 224 x 224 byte batch everything downstream (erasing, mixing, accum_iter,
-    hip_graph) sees as before.  The model must have ``input_norm``."""
+    hip_graph) sees as before.  The model must have ``input_norm``.  In the video loop (``train_video_one_epoch``) ``args.device_crop`` is a
+    util.crop.DeviceClipScaleJitterCrop or DeviceClipRandomResizedCrop: the loader yields ``((clips uint8 [B, T, Hs, Ws, 3], sizes), labels)``
+    (util.crop.pad_collate_clips) and the loop writes the normalised, resized, cropped and mirrored fp32 clips [B, 3, T, 224, 224] on the
+    device, in front of the step and outside its captured graph.  Erasing and mixing then act on that float clip -- the erasing AFTER the
+    mirror, where the reference's dataset erases before it (the shipped video configs use no erasing)."""
     optimizer = as_fused(optimizer, model)
     eraser = _device_erasing(args, cube_default=_video)
     cropper = _device_crop(args, "device_crop", DeviceRandomResizedCrop, getattr(model, "module", model), video=_video)
@@ -977,13 +1033,18 @@ def evaluate(data_loader, model, device, logger=None, base_flops=None, flops_dic
 def evaluate_video(data_loader, model, device, logger=None, base_flops=None, flops_dict=None, args=None):
     """Reference engine_finetune.py:281-356: every sample carries V views [B,V,c,t,h,w]; views are folded into the batch,
     the per-view logits averaged per sample (:302-305), then the same gather + accuracy as ``evaluate``.  ``args.stream_eval`` /
-    DYT_STREAM_EVAL=1: as in ``evaluate``."""
+    DYT_STREAM_EVAL=1: as in ``evaluate``.  ``args.device_eval_crop`` (a util.crop.DeviceClipUniformCrop): the loader yields source batches
+    -- ``((clips uint8 [B, T, Hs, Ws, 3] or [B, Vt, T, Hs, Ws, 3], sizes [B, 2]), labels)`` -- and the resize and the one or three spatial
+    views are written on the device (``_resample_clip_batch``), both forms."""
     if stream_eval_requested(args):
         return _evaluate_streaming(data_loader, model, device, logger, base_flops, flops_dict, args, video=True)
     model.eval()
     token_select, targets, predictions = [], [], []
+    cropper = _device_crop(args, "device_eval_crop", DeviceResizeCenterCrop, getattr(model, "module", model), video=True)
     for _, images, target, _ in DevicePrefetcher(data_loader, device, _verified_copy_stream(model)):
         target = target.clone()
+        if cropper is not None:
+            images = _resample_batch(getattr(model, "module", model), cropper, images)
         B, V = images.shape[0], images.shape[1]
         output, aux = model(images.flatten(0, 1))
         predictions.append(output.view(B, V, -1).mean(dim=1))

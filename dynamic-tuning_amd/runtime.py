@@ -717,6 +717,53 @@ class DyTEngine:
             self._rs_events[k].record()
         return resample_u8(pixels, self._rs_dev, None, out=self._rs_out[:n], scratch=self._rs_scratch)
 
+    def resample_clip(self, clips, sizes, draw):
+        """dyt_resample_clip_f32 on torch's current stream: the uint8 device batch of clips ``clips`` [B, T, Hs, Ws, 3] normalised with this
+        engine's input norm, resized (torch's float bilinear), windowed and mirrored as ``draw`` (a util.crop.CropDraw of clip rows, e.g.
+        ``DeviceClipScaleJitterCrop.draw_for(sizes)``) says -> fp32 [units, 3, T, 224, 224], the permuted view of a contiguous
+        [units, T, 3, 224, 224] that the video model folds without a copy.  ``sizes`` (host, [B, 2] = the clips' valid height and width,
+        or None): compared with the draw's.  Like ``resample``: ONE static device table (a row for each clip max_batch holds), a small
+        pinned host ring and a non-blocking copy on the current stream -- the kernel reads the table when it runs.  The output buffer is
+        the engine's: the returned batch is valid until the next call.  Nothing is allocated before the first call."""
+        from _lib import resample_clip_f32
+        from util.crop import table_words
+        if not hasattr(self.L, "dyt_resample_clip_f32"):
+            raise DyTError("this libdyt_hip has no dyt_resample_clip_f32 (device clip pipeline): rebuild it")
+        if not getattr(draw, "clip", False):
+            raise DyTError("resample clip: the draw holds image rows (a CropDraw with filter=2 holds clip rows)")
+        n, t = int(clips.shape[0]), int(clips.shape[1])
+        if t != self.frames:
+            raise DyTError("resample clip: the clips have %d frame(s), the engine folds %d" % (t, self.frames))
+        cap = int(self.cfg.max_batch) // self.frames
+        if draw.units > cap:
+            raise DyTError("resample clip: the draw holds %d clips of %d frames, the engine's max_batch is %d frames" % (draw.units, t, int(self.cfg.max_batch)))
+        if sizes is not None:
+            given = [tuple(int(v) for v in r) for r in (sizes.tolist() if hasattr(sizes, "tolist") else sizes)]
+            if len(given) != n or any(not (0 <= r[11] < n) or given[r[11]] != (r[0], r[1]) for r in draw.rows):
+                raise DyTError("resample clip: the draw was made for other clip sizes than the batch's")
+        try:
+            draw.check(int(clips.shape[2]), int(clips.shape[3]), n)   # an invalid row is refused before upload (the device would write zeros)
+        except ValueError as e:
+            raise DyTError(str(e))
+        words = draw.words(cap)
+        if getattr(self, "_rc_dev", None) is None:
+            self._rc_dev = torch.zeros(table_words(cap), dtype=torch.int32, device=self.device)
+            self._rc_ring = torch.zeros(self.MIX_RING, table_words(cap), dtype=torch.int32).pin_memory()
+            self._rc_events = [None] * self.MIX_RING
+            self._rc_at = 0
+            self._rc_out = torch.empty(cap, self.frames, 3, 224, 224, dtype=torch.float32, device=self.device)
+        k = self._rc_at
+        self._rc_at = (k + 1) % self.MIX_RING
+        if self._rc_events[k] is not None:
+            self._rc_events[k].synchronize()   # the copy that read this slot MIX_RING draws ago: long complete, this does not wait
+        self._rc_ring[k].copy_(torch.frombuffer(bytearray(words), dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            self._rc_dev.copy_(self._rc_ring[k], non_blocking=True)
+            if self._rc_events[k] is None:
+                self._rc_events[k] = torch.cuda.Event()
+            self._rc_events[k].record()
+        return resample_clip_f32(clips, self._rc_dev, None, out=self._rc_out[:draw.units], norm=self.input_norm, units=draw.units)
+
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on):
         self._ck(self.L.dyt_profile_enable(self.h, 1 if on else 0))

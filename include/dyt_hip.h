@@ -454,6 +454,29 @@ int64_t dyt_resample_scratch_bytes(int batch);
  * the 224 window positions.  An invalid row gives zeros.  One launch on `stream`. */
 int dyt_resample_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream);
 
+/* Device clip pipeline from byte clips (csrc/resample_clip.h, csrc/resample_clip.hip): short-side scale jitter + random crop, random resized
+ * crop, uniform one- / three-view crops and the mirror of the video loaders, as ONE two-tap resample of normalised frames --
+ * torch.nn.functional.interpolate(x, size, mode='bilinear', align_corners=False) restated bit for bit: per axis scale = (float)box / (float)full,
+ * real = max(fmaf(scale, d + 0.5f, -0.5f), 0), taps (int)real and the next one clamped to the box, weights l1 = clamp(real - i0, 0, 1),
+ * l0 = 1 - l1; per value fmaf(l0, v0, l1 * v1), columns first, then rows; v = ((float)byte / 255.0f - mean[c]) / std[c].  No antialiasing,
+ * nothing rounded to bytes.  Two context-free entries, added without an ABI version change (the version stays 5) and discovered by their
+ * symbols; the same bits from both libraries.
+ * dyt_resample_clip_f32: src uint8 [batch, frames, src_h, src_w, 3] (16-byte aligned; clips padded to one shape) -> dst fp32
+ * [units, frames, 3, 224, 224] (16-byte aligned).  table_dev is the table of dyt_resample_u8 with header word 0 (filter) = 2 ("float
+ * bilinear"; with any other value every unit is written as zeros) and the rows' 12th word = src, the index of the source clip the row
+ * reads: output unit r is written from table row r, one row serves all frames of its clip, and several rows (spatial views) may share a
+ * source clip.  A row is valid when the extent lies inside [src_h, src_w], the box inside the extent, 1 <= box, 224 <= full <= 2^23 (so
+ * that d + 0.5f is exact), the window inside full and 0 <= src < batch; there is no 2.5x bound.  Nothing of a row is used as an index
+ * before that check (64-bit comparisons); a unit whose row fails it, or that has no row (unit >= the header's units), is written as
+ * ZEROS.  The table is read when the kernel RUNS.  One launch on `stream`.  Refused with a text, before anything is enqueued: null or
+ * misaligned pointers, batch / frames / units < 1, frames or units above 65535, units > capacity, a source side < 1 or above 4096, a
+ * non-finite mean, a non-finite or zero std. */
+int dyt_resample_clip_f32(const uint8_t* src, int batch, int frames, int src_h, int src_w, float* dst, int units, const void* table_dev, int capacity, const float mean[3], const float std[3], void* stream);
+/* Debug / test entry: the taps and weights of table row `row` as the kernel computes them -> out_dev int32 [2][4][224] (16-byte aligned):
+ * axis 0 = output rows, 1 = output columns; per axis i0, i1 (relative to the box) and the bit patterns of l0, l1 of each of the 224
+ * window positions.  An invalid row gives zeros (the row's src word is not checked here: no source is read).  One launch on `stream`. */
+int dyt_resample_clip_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream);
+
 /* Streaming evaluation statistics (csrc/eval_stats.h, csrc/eval_stats.hip): a batch of logits, labels and token masks is folded into a
  * fixed-size device-resident state, so that an evaluation loop keeps no per-sample tensor.  Two context-free entries, added without an ABI
  * version change (the version stays 5) and discovered by their symbols; pure fp32 / integer, the same bits from both libraries.
