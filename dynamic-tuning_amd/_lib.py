@@ -488,6 +488,14 @@ class UnitTokBwdArgs(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("out_stride", "training", "M", "write_du", "du3_hi_only")] + \
                [(n, _f) for n in ("tau", "gs", "cat_scale", "cat_ddz_scale", "du3_scale")]
 
+
+class UnitGateArgs(ctypes.Structure):
+    """dyt_unit_gate_args (include/dyt_hip.h): GateArgs of csrc/kernels.h as a plain C struct; unset pointers are NULL."""
+    _fields_ = [(n, _vp) for n in ("u", "w", "b", "g1", "g2", "seed_dev", "soft", "maskf", "out_select", "out_logits", "keep_local", "counts")] + \
+               [(n, _u64) for n in ("seed", "subseq")] + \
+               [(n, ctypes.c_int32) for n in ("batch", "training", "out_stride", "force_first")] + \
+               [(n, _f) for n in ("tau", "threshold")]
+
 # every symbol include/dyt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dyt_last_error": (ctypes.c_char_p, []),
@@ -550,6 +558,15 @@ SYMBOLS = {
     "dyt_unit_ln_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _vp]),
     "dyt_unit_ln_param_grad": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "dyt_unit_tok_bwd": (_i, [ctypes.POINTER(UnitTokBwdArgs), _vp, _i, _vp]),
+    "dyt_unit_gate": (_i, [ctypes.POINTER(UnitGateArgs), _vp]),
+    "dyt_unit_gather_index": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "dyt_unit_ln_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "dyt_unit_ln_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "dyt_unit_adapter_ln_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "dyt_unit_ln_cls": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "dyt_unit_ln_fold_w": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "dyt_unit_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "dyt_unit_pad_convert": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dyt_gemm_bf16_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_gemm_f32_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_wgrad_scratch_floats": (ctypes.c_int64, [_i]),
@@ -568,7 +585,9 @@ SYMBOLS = {
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
                     "dyt_set_erase", "dyt_erase_images", "dyt_resample_u8", "dyt_resample_scratch_bytes", "dyt_resample_coeffs",
                     "dyt_resample_clip_f32", "dyt_resample_clip_coeffs",
-                    "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd"}
+                    "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd",
+                    "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",
+                    "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert"}
 
 _lib16 = None
 

@@ -157,7 +157,11 @@ __global__ __launch_bounds__(256) void adapter_ln_fwd_kernel(const float* __rest
     if (resid) rr.load(resid + (size_t)row * D, lane);
     xr.landed(); wr.landed(); br.landed();
     if (resid) rr.landed();
-    const float mean = xr.sum() * (1.0f / D);
+    float mean = xr.sum() * (1.0f / D);
+    // The mean is pinned in ONE register (as split2 pins its source, dyt_common.h).  Without that the 16-bit instance folds the product into
+    // the subtraction for half of a lane's channels (v_fmac x + sum * -(1/768): the product unrounded) and not for the other half, so
+    // those channels are centred on another mean than the one in `stats`: a constant row c came out as b - c 2^-25 rstd w, not as b
+    asm("" : "+v"(mean));
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < 12; ++i) { const float d = xr.v[i] - mean; sq = fmaf(d, d, sq); }

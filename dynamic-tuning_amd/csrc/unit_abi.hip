@@ -610,3 +610,130 @@ extern "C" int dyt_unit_tok_bwd(const dyt_unit_tok_bwd_args* p, float* d_gate, i
     DYT_HIP_CHECK(hipStreamSynchronize(s));
     return DYT_OK;
 }
+
+// ---- the forward row kernels alone (dispatch.hip, ln.hip, embed.hip: the token dispatcher, the LayerNorm family around it, the folded form's
+// ---- weight side and the embedding prologue): argument checks, the product's own launch_* function, synchronise.  Test-only
+// ---- (tests/test_gpu_row_fwd.py).  No arithmetic here. ----
+extern "C" int dyt_unit_gate(const dyt_unit_gate_args* p, void* stream) {
+    if (!p) { set_error("dyt_unit_gate: args is NULL"); return DYT_ERR_ARG; }
+    if (!p->u || !p->w || !p->b || !p->soft || !p->maskf || !p->keep_local || !p->counts) { set_error("dyt_unit_gate: u / w / b / soft / maskf / keep_local / counts is NULL"); return DYT_ERR_ARG; }
+    if (p->batch < 1) { set_error("dyt_unit_gate: batch = %d < 1", p->batch); return DYT_ERR_ARG; }
+    if ((p->g1 != nullptr) != (p->g2 != nullptr)) { set_error("dyt_unit_gate: g1 and g2 come together"); return DYT_ERR_ARG; }
+    if (p->training && !(p->tau > 0.f)) { set_error("dyt_unit_gate: tau = %g (> 0)", p->tau); return DYT_ERR_ARG; }
+    if ((p->out_select || p->out_logits) && p->out_stride < NP) { set_error("dyt_unit_gate: out_stride = %d < %d", p->out_stride, NP); return DYT_ERR_ARG; }
+    if (p->force_first < 0 || p->force_first > NT) { set_error("dyt_unit_gate: force_first = %d (0..%d)", p->force_first, NT); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GateArgs a;
+    a.u = p->u; a.w = p->w; a.b = p->b; a.g1 = p->g1; a.g2 = p->g2; a.batch = p->batch; a.training = p->training; a.tau = p->tau;
+    a.threshold = p->threshold; a.seed = p->seed; a.subseq = p->subseq; a.seed_dev = p->seed_dev; a.soft = p->soft; a.maskf = p->maskf;
+    a.out_select = p->out_select; a.out_logits = p->out_logits; a.out_stride = p->out_stride; a.force_first = p->force_first;
+    a.keep_local = p->keep_local; a.counts = p->counts;
+    int rc = launch_gate(a, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_gather_index(const int32_t* keep_local, const int32_t* counts, int32_t* total, const float* maskf, int32_t* row_src,
+                                     int32_t* dst_of, int batch, int32_t* drop_src, void* stream) {
+    if (!keep_local || !counts || !total || !maskf || !row_src || !dst_of) { set_error("dyt_unit_gather_index: keep_local / counts / total / maskf / row_src / dst_of is NULL"); return DYT_ERR_ARG; }
+    if (batch < 1) { set_error("dyt_unit_gather_index: batch = %d < 1", batch); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_gather_index(keep_local, counts, total, maskf, row_src, dst_of, batch, s, drop_src);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_ln_gather(const float* u, const float* w, const float* b, const int32_t* keep_local, const int32_t* counts, int32_t* total,
+                                  const float* maskf, void* out, float* stats, int32_t* row_src, int32_t* dst_of, int batch, void* out3,
+                                  int out3_f8, int32_t* drop_src, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_gather", precision); if (rc) return rc; }
+    if (!u || !w || !b || !keep_local || !counts || !total || !maskf || !stats || !row_src || !dst_of) { set_error("dyt_unit_ln_gather: u / w / b / keep_local / counts / total / maskf / stats / row_src / dst_of is NULL"); return DYT_ERR_ARG; }
+    if (batch < 1) { set_error("dyt_unit_ln_gather: batch = %d < 1", batch); return DYT_ERR_ARG; }
+    if (out3 && precision != 0) { set_error("dyt_unit_ln_gather: out3 (the split operand) exists at precision 0 only"); return DYT_ERR_ARG; }
+    if (!out && !out3) { set_error("dyt_unit_ln_gather: no output row (out and out3 are both NULL)"); return DYT_ERR_ARG; }
+    if (out3_f8 && !out3) { set_error("dyt_unit_ln_gather: out3_f8 without out3"); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_ln_gather(precision, u, w, b, keep_local, counts, total, maskf, out, reinterpret_cast<float2*>(stats), row_src, dst_of, batch, s,
+                              out3, out3_f8 ? 1 : 0, drop_src);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_ln_fwd(const float* x, const float* w, const float* b, void* out, float* stats, int rows, void* out3, int out3_f8,
+                               int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_fwd", precision); if (rc) return rc; }
+    if (!x || !w || !b || rows < 1) { set_error("dyt_unit_ln_fwd: x / w / b is NULL or rows = %d < 1", rows); return DYT_ERR_ARG; }
+    if (out3 && precision != 0) { set_error("dyt_unit_ln_fwd: out3 (the split operand) exists at precision 0 only"); return DYT_ERR_ARG; }
+    if (!out && !out3) { set_error("dyt_unit_ln_fwd: no output row (out and out3 are both NULL)"); return DYT_ERR_ARG; }
+    if (out3_f8 && !out3) { set_error("dyt_unit_ln_fwd: out3_f8 without out3"); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_ln_fwd(precision, x, w, b, out, reinterpret_cast<float2*>(stats), rows, s, out3, out3_f8 ? 1 : 0);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_adapter_ln_fwd(const float* x, const float* w, const float* b, void* out, float* stats, const float* resid, int rows,
+                                       int out_at_precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_adapter_ln_fwd", out_at_precision); if (rc) return rc; }
+    if (!x || !w || !b || !out || rows < 1) { set_error("dyt_unit_adapter_ln_fwd: x / w / b / out is NULL or rows = %d < 1", rows); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_adapter_ln_fwd(out_at_precision, x, w, b, out, reinterpret_cast<float2*>(stats), resid, rows, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_ln_cls(const float* u, const float* w, const float* b, void* out, float* stats, void* u_cls, int batch, int precision,
+                               void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_cls", precision); if (rc) return rc; }
+    if (!u || !w || !b || !out || !stats || batch < 1) { set_error("dyt_unit_ln_cls: u / w / b / out / stats is NULL or batch = %d < 1", batch); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_ln_cls(precision, u, w, b, out, reinterpret_cast<float2*>(stats), u_cls, batch, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_ln_fold_w(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf, float* cs, float* bf, int N,
+                                  int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_fold_w", precision); if (rc) return rc; }
+    if (!W || !gamma || !beta || !bias || !Wf || !cs || !bf || N < 1) { set_error("dyt_unit_ln_fold_w: W / gamma / beta / bias / Wf / cs / bf is NULL or N = %d < 1", N); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_ln_fold_w(precision, W, gamma, beta, bias, Wf, nullptr, cs, bf, N, s);   // (refuses precision 0 itself)
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_embed(const float* images, void* patches, const float* cls, const float* pos, float* x0, int batch, int precision,
+                              void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_embed", precision); if (rc) return rc; }
+    if (batch < 1) { set_error("dyt_unit_embed: batch = %d < 1", batch); return DYT_ERR_ARG; }
+    if ((images != nullptr) != (patches != nullptr)) { set_error("dyt_unit_embed: images and patches come together"); return DYT_ERR_ARG; }
+    const int ncls = (cls != nullptr) + (pos != nullptr) + (x0 != nullptr);
+    if (ncls != 0 && ncls != 3) { set_error("dyt_unit_embed: cls, pos and x0 come together"); return DYT_ERR_ARG; }
+    if (!images && !ncls) { set_error("dyt_unit_embed: nothing to do (images and cls are both NULL)"); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = 0;
+    if (images) { rc = launch_im2col(precision, images, patches, batch, s); if (rc) return rc; }
+    if (ncls) { rc = launch_cls_rows(cls, pos, x0, batch, s); if (rc) return rc; }
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_pad_convert(const float* src, void* dst, int rows, int cols, int dst_rows, int dst_cols, int transpose, int precision,
+                                    void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_pad_convert", precision); if (rc) return rc; }
+    if (!src || !dst) { set_error("dyt_unit_pad_convert: src / dst is NULL"); return DYT_ERR_ARG; }
+    if (rows < 1 || cols < 1 || dst_rows < 1 || dst_cols < 1) { set_error("dyt_unit_pad_convert: shape %d x %d -> %d x %d (all >= 1)", rows, cols, dst_rows, dst_cols); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = transpose ? launch_transpose_convert(precision, src, dst, rows, cols, dst_rows, dst_cols, s)
+                       : launch_pad_convert(precision, src, dst, rows, cols, dst_rows, dst_cols, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}

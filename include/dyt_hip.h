@@ -673,6 +673,60 @@ typedef struct {
 } dyt_unit_tok_bwd_args;
 int dyt_unit_tok_bwd(const dyt_unit_tok_bwd_args* args, float* d_gate, int precision, void* stream);
 
+/* ---- the forward row kernels alone (csrc/dispatch.hip, csrc/ln.hip, csrc/embed.hip), for tests/test_gpu_row_fwd.py: the token dispatcher,
+ * the LayerNorm family around it, the folded form's weight side and the embedding prologue.  As above: each entry checks its arguments
+ * (DYT_ERR_ARG with a text, before anything is enqueued), calls the launcher csrc/forward.hip or csrc/ctx.hip calls, and synchronises; no
+ * arithmetic of its own.  Added without an ABI version change (the version stays 5), discovered by their symbols.  `precision` and the
+ * `void*` operands as above; `stats` is (mean, rstd) pairs, 2 floats per row.  Buffer sizes are the caller's business. */
+/* gate_logits_kernel + gate_select_kernel (launch_gate).  The struct mirrors GateArgs of csrc/kernels.h field for field.  Per patch token
+ * t = b * 197 + n (n >= 1): l = <u[t], w> + b[0]; z = l (eval), (l + g1[b * 196 + n - 1] - g2[...]) / tau (training with g1), or
+ * (l + log(x) - log1p(-x)) / tau with x = u01(word 0 of Philox4x32-10(key = seed_dev ? *seed_dev : seed, counter = (t, subseq)))
+ * (training without g1); soft[t] = 1 / (1 + exp(-z)); keep = force_first > 0 ? n < force_first : soft[t] > threshold; maskf[t] = keep;
+ * out_select[b * out_stride + n - 1] = keep and out_logits[...] = l when given.  cls (n = 0): soft = maskf = 1, kept, no out_* entry.
+ * keep_local[b * 197 + 0 .. counts[b])] = the kept n of image b, ascending.
+ * DYT_ERR_ARG: NULL u / w / b / soft / maskf / keep_local / counts; batch < 1; g1 without g2 or the reverse; training with tau <= 0;
+ * out_select / out_logits with out_stride < 196; force_first outside 0..197. */
+typedef struct {
+    const float* u; const float* w; const float* b; const float* g1; const float* g2; const uint64_t* seed_dev;
+    float* soft; float* maskf; float* out_select; float* out_logits; int32_t* keep_local; int32_t* counts;
+    uint64_t seed, subseq;
+    int32_t batch, training, out_stride, force_first;
+    float tau, threshold;
+} dyt_unit_gate_args;
+int dyt_unit_gate(const dyt_unit_gate_args* args, void* stream);
+/* gather_index_kernel (launch_gather_index): from keep_local / counts / maskf as dyt_unit_gate leaves them, row_src[0:total[0]] = the kept
+ * token rows ascending, dst_of[t] = the compact row of token t or -1, total[0] = the kept tokens, total[1] = batch * 197 - total[0]
+ * (written with or without drop_src), and, when drop_src is given, drop_src[0:total[1]] = the dropped token rows ascending. */
+int dyt_unit_gather_index(const int32_t* keep_local, const int32_t* counts, int32_t* total, const float* maskf, int32_t* row_src,
+                          int32_t* dst_of, int batch, int32_t* drop_src, void* stream);
+/* ln_gather_kernel (launch_ln_gather): the same index arrays (total[1] only with drop_src) and out[dst] = LN(u[src]; w, b, eps 1e-6) for
+ * the kept rows, stats[src] = (mean, rstd).  out3 (precision 0 only; replaces out): the rows as the [rows][2*768] hi | lo split operand,
+ * out3_f8: as [hi16 768 | e4m3(hi) 768 bytes | e4m3(lo 2^12) 768 bytes]. */
+int dyt_unit_ln_gather(const float* u, const float* w, const float* b, const int32_t* keep_local, const int32_t* counts, int32_t* total,
+                       const float* maskf, void* out, float* stats, int32_t* row_src, int32_t* dst_of, int batch, void* out3, int out3_f8,
+                       int32_t* drop_src, int precision, void* stream);
+/* ln_fwd_kernel (launch_ln_fwd): out[row] = LN(x[row]; w, b, eps 1e-6), stats[row] = (mean, rstd) when stats is given; out3 / out3_f8 as
+ * above (precision 0 only, DYT_ERR_ARG at precision 1; out is then not written and may be NULL). */
+int dyt_unit_ln_fwd(const float* x, const float* w, const float* b, void* out, float* stats, int rows, void* out3, int out3_f8, int precision,
+                    void* stream);
+/* adapter_ln_fwd_kernel (launch_adapter_ln_fwd): out[row] = LN(x[row]; w, b, eps 1e-5) (+ resid[row]), of the 16-bit operand type when
+ * out_at_precision is 1, else fp32; stats and resid may be NULL. */
+int dyt_unit_adapter_ln_fwd(const float* x, const float* w, const float* b, void* out, float* stats, const float* resid, int rows,
+                            int out_at_precision, void* stream);
+/* ln_cls_kernel (launch_ln_cls): out[b] = LN(u[b * 197]; w, b, eps 1e-6) ([batch, 768]), stats[b * 197] = (mean, rstd) (the other entries
+ * of the [batch * 197] array are not written), u_cls[b] = the operand-type copy of u[b * 197] when given. */
+int dyt_unit_ln_cls(const float* u, const float* w, const float* b, void* out, float* stats, void* u_cls, int batch, int precision, void* stream);
+/* ln_fold_w_kernel (launch_ln_fold_w without the fragment-order twin): Wf[n] = AT(gamma W[n]) ([N, 768], 16-bit), cs[n] = the sum of the
+ * ROUNDED Wf[n], bf[n] = bias[n] + <W[n], beta>.  Precision 0 is the launcher's refusal (DYT_ERR_ARG). */
+int dyt_unit_ln_fold_w(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf, float* cs, float* bf, int N,
+                       int precision, void* stream);
+/* im2col_kernel (launch_im2col; images [batch, 3, 224, 224] fp32 -> patches [batch * 196, 768] with column c * 256 + i * 16 + j) when images
+ * and patches are given, and cls_rows_kernel (launch_cls_rows; x0[b * 197] = cls + pos, x0 [batch * 197, 768] fp32) when cls, pos and x0 are. */
+int dyt_unit_embed(const float* images, void* patches, const float* cls, const float* pos, float* x0, int batch, int precision, void* stream);
+/* pad_convert_kernel: dst [dst_rows, dst_cols] = src [rows, cols] (launch_pad_convert), or its transpose when `transpose`
+ * (launch_transpose_convert), rounded to the operand type, zero outside the source. */
+int dyt_unit_pad_convert(const float* src, void* dst, int rows, int cols, int dst_rows, int dst_cols, int transpose, int precision, void* stream);
+
 /* One nn.Linear (c = a w^T + bias; a [M,K], w [N,K], bias [N] or NULL, c [M,N], fp32 device pointers) through the split forms of the
  * fp32 mode: form 3 = every product as three IEEE-half products (hi*hi + hi*lo + lo*hi), form 8 = hi*hi on the f16 matrix cores plus
  * the two correction products on the fp8 (e4m3) matrix cores ("fp16f8").  K % 128 == 0, N % 128 == 0.  Unit-test entry: allocates
