@@ -222,6 +222,22 @@ def _mix_params_ptr(params):
     return ptr(params)
 
 
+def _image_source(who, images, norm, out):
+    """What mix_images and erase_images do with their batch: fp32 [n,3,224,224], uint8 [n,3,224,224] or uint8 [n,224,224,3] (which needs
+    ``norm``) -> (contiguous images, src_kind, mean, std, the fp32 [n,3,224,224] output)."""
+    import torch
+    layout = byte_image_layout(images)
+    if layout is None and not (images.dtype == torch.float32 and tuple(images.shape[1:]) == (3, 224, 224)):
+        raise DyTError("%s takes fp32 [n,3,224,224] or uint8 images (got %s %s)" % (who, images.dtype, tuple(images.shape)))
+    if layout is not None and norm is None:
+        raise DyTError("%s: uint8 images need norm=(mean, std) (the model's input_norm)" % who)
+    if out is None:
+        out = torch.empty(int(images.shape[0]), 3, 224, 224, device=images.device, dtype=torch.float32)
+    kind = 0 if layout is None else (2 if layout == "nhwc" else 1)   # csrc/image_items.h: IMAGE_SRC_F32 / _U8 / _U8_NHWC
+    mean, std = (float3(norm[0]), float3(norm[1])) if layout is not None else (None, None)
+    return images.contiguous(), kind, mean, std, out
+
+
 def mix_images(images, params, frames=1, norm=None, out=None):
     """dyt_mix_images: a device batch -- fp32 [n,3,224,224], uint8 [n,3,224,224] or uint8 [n,224,224,3] -- mixed with its mirrored batch as
     the device block ``params`` (int32[16]: csrc/mix.h MixParams) says -> fp32 [n,3,224,224], on torch's current stream.  uint8 images are
@@ -230,19 +246,10 @@ def mix_images(images, params, frames=1, norm=None, out=None):
     L = lib()
     if not hasattr(L, "dyt_mix_images"):
         raise DyTError("this libdyt_hip has no dyt_mix_images (on-device mixup): rebuild it")
-    layout = byte_image_layout(images)
-    if layout is None and not (images.dtype == torch.float32 and tuple(images.shape[1:]) == (3, 224, 224)):
-        raise DyTError("mix_images takes fp32 [n,3,224,224] or uint8 images (got %s %s)" % (images.dtype, tuple(images.shape)))
-    if layout is not None and norm is None:
-        raise DyTError("mix_images: uint8 images need norm=(mean, std) (the model's input_norm)")
     n, frames = int(images.shape[0]), int(frames)
+    images, kind, mean, std, out = _image_source("mix_images", images, norm, out)
     if frames < 1 or n % frames != 0 or (n // frames) % 2 != 0:
         raise DyTError("mix: an odd number of images / clips cannot be paired (%d images, %d frame(s) per clip)" % (n, frames))
-    images = images.contiguous()
-    if out is None:
-        out = torch.empty(n, 3, 224, 224, device=images.device, dtype=torch.float32)
-    kind = 0 if layout is None else (2 if layout == "nhwc" else 1)
-    mean, std = (float3(norm[0]), float3(norm[1])) if layout is not None else (None, None)
     with torch.cuda.device(images.device):
         check(L.dyt_mix_images(ptr(images), ptr(out), n, frames, kind, mean, std, _mix_params_ptr(params), stream_ptr()), L)
     return out
@@ -276,12 +283,8 @@ def erase_images(images, table, frames=1, norm=None, mix_params=None, out=None):
     L = lib()
     if not hasattr(L, "dyt_erase_images"):
         raise DyTError("this libdyt_hip has no dyt_erase_images (on-device random erasing): rebuild it")
-    layout = byte_image_layout(images)
-    if layout is None and not (images.dtype == torch.float32 and tuple(images.shape[1:]) == (3, 224, 224)):
-        raise DyTError("erase_images takes fp32 [n,3,224,224] or uint8 images (got %s %s)" % (images.dtype, tuple(images.shape)))
-    if layout is not None and norm is None:
-        raise DyTError("erase_images: uint8 images need norm=(mean, std) (the model's input_norm)")
     n, frames = int(images.shape[0]), int(frames)
+    images, kind, mean, std, out = _image_source("erase_images", images, norm, out)
     if frames < 1 or n < 1 or n % frames != 0:
         raise DyTError("erase: the image count is not a positive multiple of frames (%d images, %d frame(s) per clip)" % (n, frames))
     if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= 16 + 20 * n):
@@ -289,11 +292,6 @@ def erase_images(images, table, frames=1, norm=None, mix_params=None, out=None):
                        "the kernels may read a row for every image" % n)
     if mix_params is not None and (n // frames) % 2 != 0:
         raise DyTError("mix: an odd number of images / clips cannot be paired (%d images, %d frame(s) per clip)" % (n, frames))
-    images = images.contiguous()
-    if out is None:
-        out = torch.empty(n, 3, 224, 224, device=images.device, dtype=torch.float32)
-    kind = 0 if layout is None else (2 if layout == "nhwc" else 1)
-    mean, std = (float3(norm[0]), float3(norm[1])) if layout is not None else (None, None)
     with torch.cuda.device(images.device):
         check(L.dyt_erase_images(ptr(images), ptr(out), n, frames, kind, mean, std, ptr(table),
                                  None if mix_params is None else _mix_params_ptr(mix_params), stream_ptr()), L)

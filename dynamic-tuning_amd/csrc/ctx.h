@@ -160,11 +160,11 @@ struct dyt_ctx {
     int split_bwd_parts = 3;    // ... products of the GRADIENT GEMMs' contraction (3 full, 1 = dY_hi * W_hi: "fp16x3f")
     int split_bwd_attn_parts = 3;   // ... and of the split attention backward's dP / dQ / dK / dV products (3 or 1; the score recomputation keeps three)
     const float* soft_targets = nullptr; int soft_batch = 0;   // dyt_set_soft_targets: class-probability targets of the next loss evaluations
-    // dyt_set_mix: while mix_params (a DEVICE block the kernels read at run time) is set, forward_impl launches the mixing im2col and
+    // dyt_set_mix: while mix_params (a DEVICE block the kernels read at run time) is set, forward_impl launches the mixing image load and
     // dyt_step_fwd_bwd writes the class-probability rows into mix_soft ([max_batch][num_classes], allocated by the first dyt_set_mix) for its loss
     const MixParams* mix_params = nullptr; int mix_frames = 1; float* mix_soft = nullptr; size_t mix_soft_bytes = 0;
     // dyt_set_erase: while erase_table (a DEVICE table the kernels read at run time, csrc/erase.h) is set, the TRAINING passes of forward_impl
-    // launch the erasing im2col (which also mixes when mix_params is set); erase_capacity = the rows the table's allocation holds
+    // launch the erasing image load (which also mixes when mix_params is set); erase_capacity = the rows the table's allocation holds
     const void* erase_table = nullptr; int erase_capacity = 0; int erase_frames = 1;
     bool split16 = false;       // fp32 mode: frozen-weight GEMMs as three 16-bit MFMA products (DYT_OPT_F32_SPLIT16)
     void* pe_w3 = nullptr;

@@ -1,5 +1,5 @@
-// Small kernels in front of the first block (gfx950): im2col of the fp32 image batch, the cls rows, and the dtype / layout
-// converters of the weights.  (The uint8 form of im2col is input_u8.hip.)
+// Small kernels in front of the first block (gfx950): the cls rows, and the dtype / layout converters of the weights.  (The image load
+// of the patch embedding is image_load.hip.)
 #include "kernels.h"
 #include "rowhelp.h"
 
@@ -8,30 +8,6 @@ namespace dyt {
 // ------------------------------------------------------------------------------------------
 // patch embedding prologue
 // ------------------------------------------------------------------------------------------
-template <class AT>
-__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, AT* __restrict__ out, int batch) {
-    // out[(b*196 + py*14 + px)*768 + c*256 + i*16 + j] = img[b][c][py*16+i][px*16+j]; 4 consecutive j per thread
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)batch * NP * (D / 4);
-    if (idx >= total) return;
-    const int k4 = (int)(idx % (D / 4));
-    const size_t row = idx / (D / 4);
-    const int p = (int)(row % NP);
-    const int b = (int)(row / NP);
-    const int k = k4 * 4, c = k >> 8, i = (k >> 4) & 15, j = k & 15;
-    const int py = p / 14, px = p - py * 14;
-    const float4 v = *reinterpret_cast<const float4*>(img + (((size_t)b * 3 + c) * 224 + py * 16 + i) * 224 + px * 16 + j);
-    store4(out + row * D + k, v.x, v.y, v.z, v.w);
-}
-int launch_im2col(int precision, const float* images, void* out, int batch, hipStream_t s) {
-    const size_t total = (size_t)batch * NP * (D / 4);
-    const int grid = (int)((total + 255) / 256);
-    if (precision == 0) hipLaunchKernelGGL(im2col_kernel<float>, dim3(grid), dim3(256), 0, s, images, (float*)out, batch);
-    else hipLaunchKernelGGL(im2col_kernel<bf16>, dim3(grid), dim3(256), 0, s, images, (bf16*)out, batch);
-    LAUNCH_CHECK();
-    return 0;
-}
-
 __global__ void cls_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos, float* __restrict__ x0, int batch) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= batch * D) return;

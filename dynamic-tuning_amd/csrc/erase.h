@@ -1,4 +1,4 @@
-// On-device Random Erasing (dyt_set_erase, dyt_erase_images; kernels in erase.hip): the table the kernels read from device memory, the
+// On-device Random Erasing (dyt_set_erase, dyt_erase_images; the kernel is image_load.hip): the table the kernels read from device memory, the
 // per-pixel box test, the noise and every argument check, as plain functions of plain values.  A restatement of the "erase a normalised
 // batch" RandomErasing of timm / SlowFast (modes const, rand, pixel; cube = one draw per clip).  No HIP type is used here, so a host
 // compiler reads this file on its own (tools/erase_check.cpp walks it without a GPU).  The noise functions are templates over the

@@ -1,5 +1,6 @@
 // The forward pass: per-step operand refresh of the adapters and the pooling head, forward_impl, dyt_forward.
 #include "ctx.h"
+#include "image_items.h"
 
 namespace dyt {
 
@@ -216,20 +217,19 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
         // block_flops_dict.py:36-46 does): `images` IS the residual stream [B,197,768]
         DYT_HIP_CHECK(hipMemcpyAsync(S.xs[0], images, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else if (!share0) {
-        // patch embedding: im2col + GEMM (+bias +pos_embed), cls rows
-        if (erase && (flags & DYT_F_IMAGES_U8))
-            RUN(2, 0, launch_im2col_erase_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, c->erase_frames,
-                                             c->erase_table, c->erase_capacity, mix ? c->mix_params : nullptr, s));
-        else if (erase)
-            RUN(2, 0, launch_im2col_erase(P, images, T.xn, B, c->erase_frames, c->erase_table, c->erase_capacity, mix ? c->mix_params : nullptr, s));
-        else if (mix && (flags & DYT_F_IMAGES_U8))
-            RUN(2, 0, launch_im2col_mix_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, c->mix_frames, c->mix_params, s));
-        else if (mix)
-            RUN(2, 0, launch_im2col_mix(P, images, T.xn, B, c->mix_frames, c->mix_params, s));
-        else if (flags & DYT_F_IMAGES_U8)   // bytes, normalised in the load: the same operand bits as the float path on the normalised image
-            RUN(2, 0, launch_im2col_u8(P, reinterpret_cast<const uint8_t*>(images), (flags & DYT_F_IMAGES_NHWC) != 0, c->in_norm, T.xn, B, s));
-        else
-            RUN(2, 0, launch_im2col(P, images, T.xn, B, s));
+        // patch embedding: image load (im2col order; bytes are normalised in the load: the same operand bits as the float path on the
+        // normalised image) + GEMM (+bias +pos_embed), cls rows
+        {
+            ImageLoadArgs a;
+            a.src = images;
+            a.src_kind = !(flags & DYT_F_IMAGES_U8) ? IMAGE_SRC_F32 : (flags & DYT_F_IMAGES_NHWC) ? IMAGE_SRC_U8_NHWC : IMAGE_SRC_U8;
+            a.dst = T.xn; a.dst_kind = P == 0 ? IMAGE_DST_OPERAND_F32 : IMAGE_DST_OPERAND_16;
+            a.batch = B; a.frames = erase ? c->erase_frames : c->mix_frames;
+            a.norm = c->in_norm;
+            if (mix) a.mix = c->mix_params;
+            if (erase) { a.erase_table = c->erase_table; a.erase_capacity = c->erase_capacity; }
+            RUN(2, 0, launch_image_load(a, s));
+        }
         {
             GemmArgs a; a.A = T.xn; a.W = c->pe_w; a.M = B * NP; a.N = D; a.K = D;
             a.bias = c->pe_b; a.pos = c->pos; a.out_f32 = S.xs[0]; SPLIT(a, c->pe_w3);

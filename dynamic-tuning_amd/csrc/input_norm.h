@@ -1,5 +1,5 @@
-// Byte-image input (DYT_F_IMAGES_U8 / DYT_F_IMAGES_NHWC, dyt_set_input_norm, dyt_normalize_u8): the scalar formula the two kernels of
-// input_u8.hip evaluate and every argument check the entries make, as plain functions of plain values.  No HIP type and no header is
+// Byte-image input (DYT_F_IMAGES_U8 / DYT_F_IMAGES_NHWC, dyt_set_input_norm, dyt_normalize_u8): the scalar formula the byte forms of
+// image_load.hip evaluate and every argument check the entries make, as plain functions of plain values.  No HIP type and no header is
 // used here, so a host compiler reads this file on its own (tools/input_norm_check.cpp walks it without a GPU).
 #pragma once
 

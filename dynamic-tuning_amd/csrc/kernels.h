@@ -225,25 +225,21 @@ int launch_ln_cls(int precision, const float* u, const float* w, const float* b,
                   int batch, hipStream_t s);
 int launch_cls_index(int* cls_rows, int batch, hipStream_t s);
 
-// embed.hip: patch-embedding prologue and the dtype / layout converters
-int launch_im2col(int precision, const float* images, void* out, int batch, hipStream_t s);
-// input_u8.hip: the same operand from a uint8 batch ([B,3,224,224], nhwc: [B,224,224,3]), normalised with nm in the load; and the plain fp32 image
-int launch_im2col_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, hipStream_t s);
-int launch_normalize_u8(const uint8_t* src, float* dst, int batch, int nhwc, const InputNorm& nm, hipStream_t s);
-// mix.hip: the same loads with Mixup / CutMix applied (parameters in device memory), fp32 images out, class-probability rows
-int launch_im2col_mix(int precision, const float* images, void* out, int batch, int frames, const MixParams* params, hipStream_t s);
-int launch_im2col_mix_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, int frames,
-                         const MixParams* params, hipStream_t s);
-int launch_mix_images(const void* src, float* dst, int count, int frames, int src_kind, const InputNorm& nm, const MixParams* params, hipStream_t s);
+// image_load.hip: the load in front of the patch-embedding GEMM and its stand-alone forms -- one kernel family over the source kind, the
+// destination and the transform (erase_table set: Random Erasing, then the mix if `mix` is set; else `mix` set: Mixup / CutMix; else none)
+struct ImageLoadArgs {
+    const void* src = nullptr; int src_kind = 0;   // image_items.h: IMAGE_SRC_F32 [B,3,224,224], IMAGE_SRC_U8 [B,3,224,224], IMAGE_SRC_U8_NHWC [B,224,224,3]
+    void* dst = nullptr; int dst_kind = 0;         // IMAGE_DST_OPERAND_F32 / IMAGE_DST_OPERAND_16: the EPI_EMBED GEMM's A; IMAGE_DST_PLANES: fp32 [B,3,224,224]
+    int batch = 0, frames = 1;                     // images; images per clip (the mix pairs clips, a `cube` table erases per clip)
+    InputNorm norm = IN_NORM_IMAGENET;             // byte sources: normalised in the load
+    const MixParams* mix = nullptr;                // device block, read when the kernel runs
+    const void* erase_table = nullptr; int erase_capacity = 0;   // device table and the rows its allocation holds
+};
+int launch_image_load(const ImageLoadArgs& a, hipStream_t s);
+// mix.hip: class-probability rows of a Mixup / CutMix draw
 int launch_mix_targets(const int64_t* labels, float* out, int rows, int num_classes, const MixParams* params, hipStream_t s);
-// erase.hip: the same loads with Random Erasing applied first (table in device memory, `capacity` rows), then the mix when `mix` is set
-int launch_im2col_erase(int precision, const float* images, void* out, int batch, int frames, const void* table, int capacity,
-                        const MixParams* mix, hipStream_t s);
-int launch_im2col_erase_u8(int precision, const uint8_t* images, int nhwc, const InputNorm& nm, void* out, int batch, int frames,
-                           const void* table, int capacity, const MixParams* mix, hipStream_t s);
-int launch_erase_images(const void* src, float* dst, int count, int frames, int src_kind, const InputNorm& nm, const void* table, int capacity,
-                        const MixParams* mix, hipStream_t s);
 int check_image_input(int flags, const void* images);   // DYT_F_IMAGES_U8 / _NHWC of a pass: flag combination and pointer alignment, DYT_ERR_ARG with a text
+// embed.hip: the cls rows and the dtype / layout converters
 int launch_cls_rows(const float* cls, const float* pos, float* x0, int batch, hipStream_t s);
 // fp32 -> AT copy (n elements)
 int launch_convert(int precision, const float* src, void* dst, int64_t n, hipStream_t s);

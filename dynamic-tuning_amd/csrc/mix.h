@@ -1,4 +1,4 @@
-// On-device Mixup / CutMix (dyt_set_mix, dyt_mix_images, dyt_mix_targets; kernels in mix.hip): the parameter block the kernels read from
+// On-device Mixup / CutMix (dyt_set_mix, dyt_mix_images, dyt_mix_targets; kernels in image_load.hip and mix.hip): the parameter block the kernels read from
 // device memory, the pairing, the scalar formula, the per-pixel source predicate, the CutMix box and every argument check, as plain
 // functions of plain values.  A restatement of timm 0.9.12's Mixup(mode='batch', correct_lam=True) + rand_bbox.  No HIP type and no
 // header is used here, so a host compiler reads this file on its own (tools/mix_check.cpp walks it without a GPU; build that with

@@ -1,5 +1,6 @@
 // Unit-test ABI: single-kernel and sub-module entry points.  They allocate scratch and synchronise.
 #include "ctx.h"
+#include "image_items.h"
 
 namespace dyt {
 
@@ -719,7 +720,14 @@ extern "C" int dyt_unit_embed(const float* images, void* patches, const float* c
     if (!images && !ncls) { set_error("dyt_unit_embed: nothing to do (images and cls are both NULL)"); return DYT_ERR_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = 0;
-    if (images) { rc = launch_im2col(precision, images, patches, batch, s); if (rc) return rc; }
+    if (images) {
+        ImageLoadArgs a;
+        a.src = images; a.src_kind = IMAGE_SRC_F32;
+        a.dst = patches; a.dst_kind = precision == 0 ? IMAGE_DST_OPERAND_F32 : IMAGE_DST_OPERAND_16;
+        a.batch = batch;
+        rc = launch_image_load(a, s);
+        if (rc) return rc;
+    }
     if (ncls) { rc = launch_cls_rows(cls, pos, x0, batch, s); if (rc) return rc; }
     DYT_HIP_CHECK(hipStreamSynchronize(s));
     return DYT_OK;

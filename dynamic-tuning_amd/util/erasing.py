@@ -3,7 +3,7 @@
 
 This is a RESTATEMENT of the "erase a batch after normalisation" RandomErasing of timm / SlowFast (neither is a dependency): the boxes are
 drawn on the host, one draw sequence per unit -- an image, or with ``cube`` a clip whose frames share the boxes -- and the pixels are
-written on the device (csrc/erase.h, csrc/erase.hip).  The draws come from a ``random.Random`` (the reference uses the ``random`` module's
+written on the device (csrc/erase.h, csrc/image_load.hip).  The draws come from a ``random.Random`` (the reference uses the ``random`` module's
 global state, so a generator of the same seed draws the same boxes), per unit in this order:
 
     1. ``random()``; the unit is erased unless the value is > probability

@@ -720,7 +720,7 @@ int dyt_unit_ln_cls(const float* u, const float* w, const float* b, void* out, f
  * ROUNDED Wf[n], bf[n] = bias[n] + <W[n], beta>.  Precision 0 is the launcher's refusal (DYT_ERR_ARG). */
 int dyt_unit_ln_fold_w(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf, float* cs, float* bf, int N,
                        int precision, void* stream);
-/* im2col_kernel (launch_im2col; images [batch, 3, 224, 224] fp32 -> patches [batch * 196, 768] with column c * 256 + i * 16 + j) when images
+/* image_load_kernel (launch_image_load, fp32 source to the operand; images [batch, 3, 224, 224] fp32 -> patches [batch * 196, 768] with column c * 256 + i * 16 + j) when images
  * and patches are given, and cls_rows_kernel (launch_cls_rows; x0[b * 197] = cls + pos, x0 [batch * 197, 768] fp32) when cls, pos and x0 are. */
 int dyt_unit_embed(const float* images, void* patches, const float* cls, const float* pos, float* x0, int batch, int precision, void* stream);
 /* pad_convert_kernel: dst [dst_rows, dst_cols] = src [rows, cols] (launch_pad_convert), or its transpose when `transpose`

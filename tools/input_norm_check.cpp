@@ -1,5 +1,5 @@
 // CPU walk of the byte-image input's host logic (dynamic-tuning_amd/csrc/input_norm.h), checked without a GPU.
-//   * input_norm_value -- the scalar formula the two kernels of input_u8.hip evaluate -- over all 3 x 256 (channel, byte) pairs, for the
+//   * input_norm_value -- the scalar formula the byte forms of image_load.hip evaluate -- over all 3 x 256 (channel, byte) pairs, for the
 //     ImageNet and the Inception statistics, bit for bit against a table of 2 x 3 x 256 little-endian fp32 values read from the file
 //     named on the command line (tests/test_input_u8_host.py writes it from tests/golden/input_u8/input_norm_table.npz, which numpy's
 //     ((u / 255) - mean) / std in float32 produced);

@@ -17,7 +17,7 @@ def family(k):
         tile = re.search(r"ILi(\d+)ELi(\d+)E", k)
         return "gemm %s%s %s" % (m.group(1), " %sx%s" % tile.groups() if tile and m.group(1) == "nt" else "", epi.group(0) if epi else "")
     for n in ("attn_fwd", "attn_bwd_fused", "attn_bwd_dq", "attn_bwd_dkv", "wgrad_bf16", "wgrad_reduce", "tok_bwd", "ln_bwd", "ln_fwd", "ln_gather", "gate_logits",
-              "gate_select", "bwd_prep", "reduce_partials", "head_", "loss_", "adamw", "im2col", "prep_adapters", "fillBuffer", "copyBuffer"):
+              "gate_select", "bwd_prep", "reduce_partials", "head_", "loss_", "adamw", "image_load", "prep_adapters", "fillBuffer", "copyBuffer"):
         if n in k:
             return n.rstrip("_")
     return "other"

@@ -1,4 +1,4 @@
-"""Kernel time of im2col_u8_kernel (both byte layouts) next to im2col_kernel, in one process.
+"""Kernel time of image_load_kernel from both byte layouts next to the fp32 source, in one process.
 
 Run mode (under ``rocprofv3 --kernel-trace --output-format csv``): fp16 eval forwards at B = 128 through one inference-only context,
 alternating float images, uint8 [B,3,224,224] and uint8 [B,224,224,3] -- REPS rounds of the three, the first WARM rounds are warm-up.
@@ -8,6 +8,7 @@ Parse mode: ``python tools/probes/input_u8_times.py --parse TRACE.csv [...]`` pr
 launches after warm-up, and the bytes each moves over that time."""
 import csv
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -36,17 +37,18 @@ def run():
 
 def parse(paths):
     out_bytes = B * 196 * 768 * 2   # the fp16 operand
-    moved = {"im2col_kernel": B * PIX * 4 + out_bytes, "im2col_u8_kernel": B * PIX + out_bytes}
+    moved = {0: B * PIX * 4 + out_bytes, 1: B * PIX + out_bytes, 2: B * PIX + out_bytes}   # by source kind (csrc/image_items.h)
     for path in paths:
         rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
         runs = {}
         for r in rows:
             name = r["Kernel_Name"]
-            if "im2col" in name:
+            if "image_load_kernel" in name:
                 runs.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
         for name, d in sorted(runs.items()):
             t = d[WARM:]
-            kind = "im2col_u8_kernel" if "im2col_u8" in name else "im2col_kernel"
+            m = re.search(r"image_load_kernel<(\d)", name) or re.search(r"image_load_kernelILi(\d)E", name)   # demangled or not
+            kind = int(m.group(1))
             mean = sum(t) / len(t)
             print("%-86s mean %7.2f us  min %7.2f  max %7.2f  (%d launches)  %5.1f MB -> %5.2f TB/s" % (
                 name[:86], mean, min(t), max(t), len(t), moved[kind] / 1e6, moved[kind] / mean / 1e6))
