@@ -494,6 +494,18 @@ class UnitGateArgs(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("batch", "training", "out_stride", "force_first")] + \
                [(n, _f) for n in ("tau", "threshold")]
 
+class UnitAttnFwdArgs(ctypes.Structure):
+    """dyt_unit_attn_fwd_args (include/dyt_hip.h): AttnFwdArgs of csrc/kernels.h as a plain C struct; unset pointers are NULL."""
+    _fields_ = [(n, _vp) for n in ("q", "k", "v", "q_hi", "k_hi", "v_hi", "q_lo", "k_lo", "v_lo", "out", "out3", "q16", "k16", "v16", "o16", "lse")] + \
+               [(n, ctypes.c_int32) for n in ("planar", "out3_f8", "lse_optional", "split16", "parts", "batch")]
+
+
+class UnitAttnBwdArgs(ctypes.Structure):
+    """dyt_unit_attn_bwd_args (include/dyt_hip.h): AttnBwdArgs of csrc/kernels.h as a plain C struct; unset pointers are NULL."""
+    _fields_ = [(n, _vp) for n in ("q", "k", "v", "out", "dout", "lse", "delta", "dqkv", "dqkv3")] + \
+               [(n, ctypes.c_int32) for n in ("out_ld", "out_hi_only", "split16", "grad_parts", "q_tiles", "batch")] + \
+               [("s3", _f)]
+
 # every symbol include/dyt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dyt_last_error": (ctypes.c_char_p, []),
@@ -565,6 +577,8 @@ SYMBOLS = {
     "dyt_unit_ln_fold_w": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "dyt_unit_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "dyt_unit_pad_convert": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dyt_unit_attn_fwd": (_i, [ctypes.POINTER(UnitAttnFwdArgs), _i, _vp]),
+    "dyt_unit_attn_bwd": (_i, [ctypes.POINTER(UnitAttnBwdArgs), _i, _vp]),
     "dyt_gemm_bf16_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_gemm_f32_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_wgrad_scratch_floats": (ctypes.c_int64, [_i]),
@@ -585,7 +599,7 @@ OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u
                     "dyt_resample_clip_f32", "dyt_resample_clip_coeffs",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd",
                     "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",
-                    "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert"}
+                    "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert", "dyt_unit_attn_fwd", "dyt_unit_attn_bwd"}
 
 _lib16 = None
 

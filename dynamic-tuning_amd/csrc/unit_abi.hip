@@ -745,3 +745,38 @@ extern "C" int dyt_unit_pad_convert(const float* src, void* dst, int rows, int c
     DYT_HIP_CHECK(hipStreamSynchronize(s));
     return DYT_OK;
 }
+
+// ---- the attention kernels alone (attention.hip, attention_v2.hip): the structs are AttnFwdArgs / AttnBwdArgs of kernels.h field for field, the
+// ---- kernel is whatever attn_fwd_route() / attn_bwd_route() pick from them and the three process-wide switches.  The launcher's own checks
+// ---- refuse a bad call; no arithmetic, no kernels, no layout conversion here.  Test-only (tests/test_gpu_unit_attention.py). ----
+extern "C" int dyt_unit_attn_fwd(const dyt_unit_attn_fwd_args* p, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_attn_fwd", precision); if (rc) return rc; }
+    if (!p) { set_error("dyt_unit_attn_fwd: args is NULL"); return DYT_ERR_ARG; }
+    if (p->batch < 1) { set_error("dyt_unit_attn_fwd: batch = %d < 1", p->batch); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AttnFwdArgs a;
+    a.q = p->q; a.k = p->k; a.v = p->v; a.planar = p->planar != 0;
+    a.q_hi = p->q_hi; a.k_hi = p->k_hi; a.v_hi = p->v_hi; a.q_lo = p->q_lo; a.k_lo = p->k_lo; a.v_lo = p->v_lo;
+    a.out = p->out; a.out3 = p->out3; a.out3_f8 = p->out3_f8 != 0;
+    a.q16 = p->q16; a.k16 = p->k16; a.v16 = p->v16; a.o16 = p->o16;
+    a.lse = p->lse; a.lse_optional = p->lse_optional != 0; a.split16 = p->split16 != 0; a.parts = p->parts; a.batch = p->batch;
+    int rc = launch_attn_fwd(precision, a, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_attn_bwd(const dyt_unit_attn_bwd_args* p, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_attn_bwd", precision); if (rc) return rc; }
+    if (!p) { set_error("dyt_unit_attn_bwd: args is NULL"); return DYT_ERR_ARG; }
+    if (p->batch < 1) { set_error("dyt_unit_attn_bwd: batch = %d < 1", p->batch); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AttnBwdArgs a;
+    a.q = p->q; a.k = p->k; a.v = p->v; a.out = p->out; a.out_ld = p->out_ld; a.dout = p->dout; a.lse = p->lse; a.delta = p->delta;
+    a.dqkv = p->dqkv; a.dqkv3 = p->dqkv3; a.s3 = p->s3; a.out_hi_only = p->out_hi_only != 0; a.split16 = p->split16 != 0;
+    a.grad_parts = p->grad_parts; a.q_tiles = p->q_tiles; a.batch = p->batch;
+    int rc = launch_attn_bwd(precision, a, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}

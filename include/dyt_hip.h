@@ -727,6 +727,31 @@ int dyt_unit_embed(const float* images, void* patches, const float* cls, const f
  * (launch_transpose_convert), rounded to the operand type, zero outside the source. */
 int dyt_unit_pad_convert(const float* src, void* dst, int rows, int cols, int dst_rows, int dst_cols, int transpose, int precision, void* stream);
 
+/* ---- the attention kernels alone (csrc/attention.hip, csrc/attention_v2.hip), for tests/test_gpu_unit_attention.py.  The structs mirror
+ * AttnFwdArgs / AttnBwdArgs of csrc/kernels.h field for field (bool as int32); unset pointers are NULL.  The entries check the struct
+ * pointer, `precision` and batch >= 1, call launch_attn_fwd / launch_attn_bwd, return the launcher's error (every refusal of
+ * csrc/attn_route.h and of the launchers arrives as DYT_ERR_ARG with a text, before anything is enqueued) and synchronise: no arithmetic,
+ * no kernel, no layout conversion of their own.  The kernel is the one attn_fwd_route() / attn_bwd_route() pick from the fields and the
+ * process-wide DYT_OPT_F32_SPLIT16 / DYT_OPT_ATTN_BWD_FUSED / DYT_OPT_ATTN_V2 (dyt_set_global_option).  Added without an ABI version change.
+ * q / k / v [batch*12][197][64] of the operand type (fp32 at precision 0), q already times 1/8; the planar form takes the 16-bit hi / lo
+ * planes in the same layout.  out / o16 [batch*197][768], out3 [batch*197][SPLIT_A*768] 16-bit words, lse [batch*12][197] fp32 (natural log). */
+typedef struct {
+    const void* q; const void* k; const void* v;
+    const void* q_hi; const void* k_hi; const void* v_hi; const void* q_lo; const void* k_lo; const void* v_lo;
+    void* out; void* out3; void* q16; void* k16; void* v16; void* o16; float* lse;
+    int32_t planar, out3_f8, lse_optional, split16, parts, batch;
+} dyt_unit_attn_fwd_args;
+int dyt_unit_attn_fwd(const dyt_unit_attn_fwd_args* args, int precision, void* stream);
+/* out [batch*197][out_ld] (out_ld 0 = 768), dout [batch*197][768], delta [batch*12][197] fp32 scratch (= rowsum(dout * out) where the route
+ * writes it), dqkv [batch*197][2304] = (dq / 8 | dk | dv), dqkv3 = dqkv * s3 as the [batch*197][3*2304] split operand (precision 0). */
+typedef struct {
+    const void* q; const void* k; const void* v; const void* out; const void* dout; const float* lse;
+    float* delta; void* dqkv; void* dqkv3;
+    int32_t out_ld, out_hi_only, split16, grad_parts, q_tiles, batch;
+    float s3;
+} dyt_unit_attn_bwd_args;
+int dyt_unit_attn_bwd(const dyt_unit_attn_bwd_args* args, int precision, void* stream);
+
 /* One nn.Linear (c = a w^T + bias; a [M,K], w [N,K], bias [N] or NULL, c [M,N], fp32 device pointers) through the split forms of the
  * fp32 mode: form 3 = every product as three IEEE-half products (hi*hi + hi*lo + lo*hi), form 8 = hi*hi on the f16 matrix cores plus
  * the two correction products on the fp8 (e4m3) matrix cores ("fp16f8").  K % 128 == 0, N % 128 == 0.  Unit-test entry: allocates

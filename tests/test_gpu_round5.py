@@ -1,7 +1,8 @@
 """GPU tests added in round 5 (pytest -m gpu), all through the C ABI.
   * the round-5 attention kernels (csrc/attention_v2.hip) against an fp64 restatement of Attention.forward
     (models/vision_transformer_IN21K.py:60-70 of the reference) and its autograd backward, against the round 1-4 kernels, and
-    bit for bit against themselves (run to run, and cls-only tail vs full gradient)."""
+    bit for bit against themselves (run to run; the cls-only tail against the full gradient is held by
+    tests/test_gpu_unit_attention.py::test_cls_only_tail_equals_the_full_gradient)."""
 import pytest
 import torch
 
