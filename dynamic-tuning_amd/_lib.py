@@ -539,6 +539,8 @@ SYMBOLS = {
     "dyt_trainable_offset": (_i, [_vp, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "dyt_forward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "dyt_backward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dyt_forward_taps": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "dyt_backward_tokens": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dyt_loss": (_i, [_vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "dyt_adamw": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _f, _f, _f, _f, _f, _vp]),
     "dyt_adamw_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _vp]),
@@ -566,6 +568,7 @@ SYMBOLS = {
     "dyt_gate_compact": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dyt_unit_bwd_prep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "dyt_unit_ln_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _i, _vp]),
+    "dyt_unit_ln_bwd_tap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _f, _i, _vp, _i, _vp]),
     "dyt_unit_ln_param_grad": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "dyt_unit_tok_bwd": (_i, [ctypes.POINTER(UnitTokBwdArgs), _vp, _i, _vp]),
     "dyt_unit_gate": (_i, [ctypes.POINTER(UnitGateArgs), _vp]),
@@ -599,7 +602,8 @@ OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u
                     "dyt_resample_clip_f32", "dyt_resample_clip_coeffs",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd",
                     "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",
-                    "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert", "dyt_unit_attn_fwd", "dyt_unit_attn_bwd"}
+                    "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert", "dyt_unit_attn_fwd", "dyt_unit_attn_bwd",
+                    "dyt_forward_taps", "dyt_backward_tokens", "dyt_unit_ln_bwd_tap"}
 
 _lib16 = None
 
@@ -655,6 +659,39 @@ def check(rc, L=None):
         if not msg and _lib16 is not None and L is None:
             msg = _lib16.dyt_last_error().decode()
         raise DyTError("libdyt_hip: %s (code %d)" % (msg, rc))
+
+
+def ptr_array(tensors, n):
+    """``n`` device pointers in host memory (dyt_forward_taps / dyt_backward_tokens): entry i = tensors[i]'s pointer, NULL where it is None.
+    None when every entry is None."""
+    if tensors is None or all(t is None for t in tensors):
+        return None
+    assert len(tensors) == n, (len(tensors), n)
+    arr = (ctypes.c_void_p * n)()
+    for i, t in enumerate(tensors):
+        if t is not None:
+            assert t.is_cuda and t.is_contiguous(), "libdyt_hip needs contiguous device tensors"
+            arr[i] = t.data_ptr()
+    return arr
+
+
+def check_out_indices(out_indices, depth):
+    """``out_indices`` of forward_features as a tuple of block indices in [0, depth): distinct ints, negative values count from the end
+    (the reference backbone's out_indices=[3, 5, 7, 11]).  Anything else: ValueError."""
+    if isinstance(out_indices, (str, bytes)) or not hasattr(out_indices, "__iter__"):
+        raise ValueError("out_indices=%r: a sequence of block indices (ints in [-%d, %d))" % (out_indices, depth, depth))
+    out = []
+    for i in out_indices:
+        if isinstance(i, bool) or not isinstance(i, int):
+            raise ValueError("out_indices=%r: %r is not an int" % (tuple(out_indices), i))
+        if not -depth <= i < depth:
+            raise ValueError("out_indices=%r: %d is outside [-%d, %d) (the model has %d blocks)" % (tuple(out_indices), i, depth, depth, depth))
+        out.append(i + depth if i < 0 else i)
+    if len(set(out)) != len(out):
+        raise ValueError("out_indices=%r: block indices must be distinct (after counting negative values from the end: %r)" % (tuple(out_indices), tuple(out)))
+    if not out:
+        raise ValueError("out_indices=(): name at least one block, or pass None for the tokens alone")
+    return tuple(out)
 
 
 def ptr(t):

@@ -97,13 +97,23 @@ static int pool_backward(dyt_ctx* c, Slot& S, const float* tr, const float* dlog
 // ev_split (optional) is recorded on `s` once the gradients of the head and of every block >= split are enqueued
 int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float* dlogits, const float* dtoken_select,
                        const float* dtok, const float* dtoken_logits, float* grad, hipStream_t s,
-                       hipEvent_t ev_split, int split) {
+                       hipEvent_t ev_split, int split, const TokenGrads* tg) {
     { int rc = refuse_inference(c, "the backward pass"); if (rc) return rc; }
     if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
     Slot& S = c->slots[slot];
     Transients& T = S.T;
     if (!S.valid) { set_error("slot %d holds no saved forward (call dyt_forward with DYT_F_SAVE)", slot); return DYT_ERR_STATE; }
-    if (!dlogits || !grad || !trainable) { set_error("null argument"); return DYT_ERR_ARG; }
+    // a slot serves the entry point of its own kind of pass
+    if (S.tokens && !tg) {
+        set_error("slot %d holds a token-level pass (dyt_forward_taps / DYT_F_TOKENS_OUT): its backward is dyt_backward_tokens, not dyt_backward", slot);
+        return DYT_ERR_STATE;
+    }
+    if (!S.tokens && tg) {
+        set_error("slot %d holds a pass that ran the head (dyt_forward without DYT_F_TOKENS_OUT): its backward is dyt_backward, not dyt_backward_tokens "
+                  "(save a token-level pass with dyt_forward_taps and DYT_F_SAVE)", slot);
+        return DYT_ERR_STATE;
+    }
+    if ((!dlogits && !tg) || !grad || !trainable) { set_error("null argument"); return DYT_ERR_ARG; }
     // b16 ("fp16x3h"): the saved pass came from the exact (split fp32) forward, this backward runs in the 16-bit mode: P = 1, the
     // 16-bit copies of the saved tensors and of the dgrad matrices, none of the split forms below
     const bool b16 = S.saved16;
@@ -134,8 +144,24 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
     hipStream_t sb = nullptr;
     { int rc = branch_stream(c, S, &sb); if (rc) return rc; }
 
-    const bool cls_tail = c->cls_tail;
-    if (c->frames > 1) {
+    const bool cls_tail = c->cls_tail && !tg;   // a token-level pass computed and saved every row of the last block: it is a block like the others
+    const float* const* dtaps = tg ? tg->dtaps : nullptr;
+    if (tg) {
+        // top of the stack: g = LNbwd_final(dtokens) + dtaps[depth-1], in fp32 whatever the mode (the un-fused bwd_prep below then makes g_at / dmask,
+        // as behind head_bwd).  The frozen final norm has no parameter gradient; its statistics over all rows are recomputed (no pass keeps them).
+        // With DYT_CREATE_FC_NORM the final norm is an identity: g = dtokens + dtaps[depth-1].
+        const float* top = dtaps ? dtaps[depth - 1] : nullptr;
+        if (tg->dtokens && !c->fc_norm) {
+            float2* st = reinterpret_cast<float2*>(T.delta);   // [M] of the [B,12,197] floats the first attention backward writes later
+            RUN(2, 0, launch_ln_stats(S.xs[depth], st, M, s));
+            RUN(2, 0, launch_ln_bwd(0, tg->dtokens, S.xs[depth], st, c->norm_w, top, g, M, nullptr, nullptr, nullptr, nullptr, 1.0f, s));
+        } else if (tg->dtokens || top) {
+            RUN(2, 0, launch_rows_add(tg->dtokens ? tg->dtokens : top, tg->dtokens ? top : nullptr, g, M, s));
+        } else {
+            DYT_HIP_CHECK(hipMemsetAsync(g, 0, (size_t)M * D * sizeof(float), s));
+        }
+        { const int l = depth; CK("tokens_top g", g, (size_t)M * D * 4); }
+    } else if (c->frames > 1) {
         int rc = pool_backward(c, S, trainable, dlogits, grad, s);
         if (rc) return rc;
     } else {
@@ -356,7 +382,8 @@ int dyt::backward_impl(dyt_ctx* c, int slot, const float* trainable, const float
             if (g_at) POISON(256, g_at, (size_t)M * D * atb);
             ISO(4, RUN(2, 0, launch_ln_bwd(P, T.dxn, S.xs[l], L.st1, W.ln1_w, g16 ? nullptr : g, g16 ? nullptr : g, M, g_at, student ? (b16 ? Ln.h16 : Ln.h) : nullptr,
                                     (!dense && !h_by_token) ? Ln.dst_of : nullptr, student ? T.dmask : nullptr, gs, s,
-                                    (split_prod && l > 1) ? T.g3 : nullptr, c->split_gs, c->split_bwd_parts == 1, g16 ? T.du_at : nullptr)););
+                                    (split_prod && l > 1) ? T.g3 : nullptr, c->split_gs, c->split_bwd_parts == 1, g16 ? T.du_at : nullptr,
+                                    dtaps ? dtaps[l - 1] : nullptr)););   // xs[l] is taps[l - 1]: its gradient joins the stream inside this kernel
             g3_ready = split_prod && l > 1;
             if (!g16) CK("ln_bwd g", g, (size_t)M * D * 4);
             if (g_at) CK("ln_bwd g_at", g_at, (size_t)M * D * atb);
@@ -379,4 +406,21 @@ extern "C" int dyt_backward(dyt_ctx* c, int slot, const float* dlogits, const fl
     if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
     return backward_impl(c, slot, c->slots[slot].trainable, dlogits, dtoken_select, dtok, dtoken_logits, grad_flat,
                          static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dyt_backward_tokens(dyt_ctx* c, int slot, const float* dtokens, const float* const* dtaps, const float* dtoken_select,
+                                   const float* dtok, const float* dtoken_logits, float* grad_flat, void* stream) {
+    if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
+    { int rc = refuse_inference(c, "dyt_backward_tokens"); if (rc) return rc; }
+    if (c->frames > 1) {
+        set_error("dyt_backward_tokens: image model only (frames=%d: the video model trains through its attentive pooling head, dyt_backward)", c->frames);
+        return DYT_ERR_ARG;
+    }
+    if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
+    bool any = dtokens || dtoken_select || dtok || dtoken_logits;
+    for (int i = 0; dtaps && i < c->cfg.depth; ++i) any = any || dtaps[i];
+    if (!any) { set_error("dyt_backward_tokens: every gradient input is NULL (dtokens, dtaps[0..%d], dtoken_select, dtok_uniform, dtoken_logits)", c->cfg.depth - 1); return DYT_ERR_ARG; }
+    TokenGrads tg; tg.dtokens = dtokens; tg.dtaps = dtaps;
+    return backward_impl(c, slot, c->slots[slot].trainable, nullptr, dtoken_select, dtok, dtoken_logits, grad_flat,
+                         static_cast<hipStream_t>(stream), nullptr, 0, &tg);
 }

@@ -109,6 +109,7 @@ struct Slot {
     float* head_part = nullptr;   // dyt_ctx::wide_head, training layout: [ceil(C/1024)][max_batch][768] class-slice partial sums of the head's dx (per slot: the two passes' backward run on two streams)
     int batch = 0, flags = 0;
     bool valid = false;
+    bool tokens = false;     // the saved pass is token-level (DYT_F_TOKENS_OUT): every row of the last block is saved, no head ran -- dyt_backward_tokens' slot, not dyt_backward's
     bool saved16 = false;    // the saved pass holds the 16-bit tensors of a 16-bit backward (dyt_ctx::bwd16)
     const float* trainable = nullptr;  // flat trainable buffer the saved pass was computed with
     // stochastic depth (dyt_set_drop_path): the per-image branch factors [2][depth][batch] of this slot's passes -- drawn by the library
@@ -116,6 +117,8 @@ struct Slot {
     float* dp_own = nullptr; const float* dp_inject = nullptr; const float* dp = nullptr;
     float* gscr = nullptr;   // DYT_OPT_LEARNABLE_SCALE: [depth * layer_stride] the backward's up-projection gradients before the chain rule through the scale
 };
+// dyt_backward_tokens: the gradient enters at the tokens and the taps instead of at the logits
+struct TokenGrads { const float* dtokens = nullptr; const float* const* dtaps = nullptr; };
 struct ProfRec { int cat; double flops; hipEvent_t a, b; const int* m_dev; int M; };
 
 struct dyt_ctx {
@@ -242,11 +245,12 @@ int branch_stream(dyt_ctx* c, Slot& S, hipStream_t* out);
 int forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flags, const float* trainable,
                  const float* g1, const float* g2, const uint8_t* keep_mask, uint64_t seed, float* logits,
                  float* token_select, float* token_logits, bool do_prep, hipStream_t s,
-                 const Slot* share0 = nullptr, hipEvent_t ev_b0_record = nullptr, hipEvent_t ev_b0_wait = nullptr);
+                 const Slot* share0 = nullptr, hipEvent_t ev_b0_record = nullptr, hipEvent_t ev_b0_wait = nullptr,
+                 float* const* taps = nullptr);   // taps[l] (null: not wanted) := xs[l + 1], dyt_forward_taps
 // backward.hip
 int backward_impl(dyt_ctx* c, int slot, const float* trainable, const float* dlogits, const float* dtoken_select,
                   const float* dtok, const float* dtoken_logits, float* grad, hipStream_t s,
-                  hipEvent_t ev_split = nullptr, int split = 0);
+                  hipEvent_t ev_split = nullptr, int split = 0, const TokenGrads* tg = nullptr);
 // debug.hip (measurement hooks behind CK / ISO / POISON)
 bool dbg_ck_on();
 int dbg_ck_reset(hipStream_t s);

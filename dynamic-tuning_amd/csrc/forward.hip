@@ -163,7 +163,7 @@ static int pool_forward(dyt_ctx* c, Slot& S, const float* tr, float* logits, int
 int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flags, const float* trainable,
                       const float* g1, const float* g2, const uint8_t* keep_mask, uint64_t seed, float* logits,
                       float* token_select, float* token_logits, bool do_prep, hipStream_t s,
-                      const Slot* share0, hipEvent_t ev_b0_record, hipEvent_t ev_b0_wait) {
+                      const Slot* share0, hipEvent_t ev_b0_record, hipEvent_t ev_b0_wait, float* const* taps) {
     // share0: reuse another pass's embedding + block-0 attention branch (same images, same frozen weights):
     //         its u / u_at of block 0 become this pass's (the step function aliases the pointers).
     if (slot < 0 || slot >= c->cfg.slots) { set_error("slot %d out of range", slot); return DYT_ERR_ARG; }
@@ -425,6 +425,8 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
             if (tail && c->inf) { a.splitk_ws = T.sk_ws; a.splitk_ws_bytes = (size_t)(DM / 256 + 1) * c->cfg.max_batch * D * sizeof(float); }   // (same decision in run_bf16: either size holds the B-row partials)
             RUN_GEMM(EPI_FC2, a);
         }
+        // dyt_forward_taps: the residual stream behind this block, copied while it is there (an inference-only context keeps two streams in turn)
+        if (taps && taps[l]) DYT_HIP_CHECK(hipMemcpyAsync(taps[l], xo, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (tokens_out) {   // the block stack's output tokens instead of the head: `logits` receives [B,197,768]
         DYT_HIP_CHECK(hipMemcpyAsync(logits, S.xs[depth], (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -445,7 +447,7 @@ int dyt::forward_impl(dyt_ctx* c, int slot, const float* images, int B, int flag
                                       S.head_stats, logits, B, c->cfg.num_classes, s, hx_stride));
     }
     c->pass_ran = true;
-    S.batch = B; S.flags = flags; S.valid = save && !tokens_in && !tokens_out; S.trainable = trainable; S.saved16 = save16;   // token-level passes are forward only
+    S.batch = B; S.flags = flags; S.valid = save && !tokens_in; S.tokens = tokens_out; S.trainable = trainable; S.saved16 = save16;   // (a pass on a caller's residual stream is forward only; images in, tokens out: dyt_backward_tokens)
     return DYT_OK;
 }
 
@@ -459,4 +461,21 @@ extern "C" int dyt_forward(dyt_ctx* c, int slot, const float* images, int batch,
     }
     return forward_impl(c, slot, images, batch, flags, trainable, g1, g2, keep_mask, seed, logits, token_select,
                         token_logits, true, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dyt_forward_taps(dyt_ctx* c, int slot, const float* images, int batch, int flags, const float* trainable,
+                                const float* g1, const float* g2, const uint8_t* keep_mask, uint64_t seed, float* tokens,
+                                float* const* taps, float* token_select, float* token_logits, void* stream) {
+    if (!c) { set_error("null ctx"); return DYT_ERR_ARG; }
+    if (!(flags & DYT_F_TOKENS_OUT) || (flags & DYT_F_TOKENS_IN)) {
+        set_error("dyt_forward_taps: flags 0x%x -- a pass from images to tokens (DYT_F_TOKENS_OUT without DYT_F_TOKENS_IN)", flags);
+        return DYT_ERR_ARG;
+    }
+    if (c->frames > 1) { set_error("dyt_forward_taps: image model only (frames=%d: the video model pools every frame's tokens inside its head)", c->frames); return DYT_ERR_ARG; }
+    if (slot >= 0 && slot < c->cfg.slots) {  // a stand-alone pass owns its block-0 buffers
+        Slot& S = c->slots[c->inf ? 0 : slot];
+        S.L[0].u = S.u0_own; S.L[0].u_at = S.u0_at_own; S.L[0].u16 = S.u0_16_own; S.L[0].ln_part = S.part0_own;
+    }
+    return forward_impl(c, slot, images, batch, flags, trainable, g1, g2, keep_mask, seed, tokens, token_select,
+                        token_logits, true, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, taps);
 }

@@ -177,7 +177,10 @@ int launch_ln_fwd_f32out(const float* x, const float* w, const float* b, float* 
 // dx_out[row] = base[row] + LNbwd(dy[row]; x[row], stats[row], w)
 int launch_ln_bwd(int precision, const void* dy, const float* x, const float2* stats, const float* w, const float* base,
                   float* dx_out, int rows, void* g_at, const void* h_next, const int* dst_of_next, float* dmask_next,
-                  float gs, hipStream_t s, void* out3 = nullptr, float s3 = 1.0f, int out3_hi_only = 0, const void* base_at = nullptr);   // base_at: the stream as a 16-bit gs-scaled operand copy instead of `base` (dx_out may then be null)   // out3: + dx * s3 as a [rows][3*768] split operand (fp32 mode)   // gs: factor carried by the 16-bit gradient operands dy (in) and g_at (out)
+                  float gs, hipStream_t s, void* out3 = nullptr, float s3 = 1.0f, int out3_hi_only = 0, const void* base_at = nullptr, const float* tap = nullptr);   // tap: + an fp32 [rows][768] row added behind base / base_at (the tapped instantiations, dyt_backward_tokens)   // base_at: the stream as a 16-bit gs-scaled operand copy instead of `base` (dx_out may then be null)   // out3: + dx * s3 as a [rows][3*768] split operand (fp32 mode)   // gs: factor carried by the 16-bit gradient operands dy (in) and g_at (out)
+// stats[row] = (mean, rstd) of x[row] (eps 1e-6) alone; out[row] = a[row] + b[row] (b null: a copy), fp32 [rows][768]
+int launch_ln_stats(const float* x, float2* stats, int rows, hipStream_t s);
+int launch_rows_add(const float* a, const float* b, float* out, int rows, hipStream_t s);
 
 // the adapter's own LayerNorm (dyt_config::adapter_ln; reference models/dynamic_adapter.py:95-98,121-122,132-133; eps 1e-5): out = LN(x) w + b (+ resid),
 // out of the 16-bit operand type (out_at_precision != 0) or fp32; stats[row] = (mean, rstd)

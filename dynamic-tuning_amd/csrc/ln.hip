@@ -52,6 +52,63 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 
 // dx = base + LNbwd(dy).  Optionally also does the NEXT (lower) block's backward prep on the row it just
 // produced (saves re-reading the 77 MB gradient): AT copy of dx, and <dx, h_next> for the gate gradient.
+// The kernel's body, shared by the two kernels below as TEXT (a macro, not a device function: behind a function the compiler orders the
+// operands of some commutative instructions of the untapped kernels differently, and those kernels are to stay the code they were).
+// Every load of the row is issued up front and completed by ONE full drain that names all of them (DYT_PIN*, dyt_common.h).
+// base_at (fp16 mode): the gradient stream this row's LayerNorm gradient is added to arrives as the 16-bit, gs-scaled copy the kernel before
+// wrote for its GEMM (tok_bwd's du_at) instead of as an fp32 [M,768] stream; dx == null: no fp32 copy is written either.
+// TAP (a compile-time constant; token-gradient entry, dyt_backward_tokens): one more fp32 row, the caller's gradient of this residual-stream
+// snapshot, loaded up front with the others (same drain) and added in fp32 behind base / base_at -- before dx, out3, g_at and <dx, h_next>
+// are formed, so a tap gradient costs one row read and no rounding of its own.
+#define LN_BWD_BODY(TAP) \
+    const int lane = threadIdx.x & 63;                                               \
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);                             \
+    if (row >= rows) return;                                                         \
+    Row12 g, xr, wr, br, tr;                                                         \
+    g.load_at(dy + (size_t)row * D, lane);                                           \
+    xr.load_nt(x + (size_t)row * D, lane);                                           \
+    wr.load(w, lane);                                                                \
+    float2 st = stats[row];                                                          \
+    int r = dst_of_next ? dst_of_next[row] : row;                                    \
+    if (base_at) br.load_at(base_at + (size_t)row * D, lane);                        \
+    else if (base) br.load(base + (size_t)row * D, lane);                            \
+    if (TAP) tr.load(tap + (size_t)row * D, lane);                                   \
+    LN_ROWPIN(g); LN_ROWPIN(xr); LN_ROWPIN(wr);                                      \
+    LN_SCALPIN3(st.x, st.y, r);                                                      \
+    if (base || base_at) LN_ROWPIN(br);                                              \
+    if (TAP) LN_ROWPIN(tr);                                                          \
+    ln_bwd_row(g, xr, wr, st);                                                       \
+_Pragma("unroll")                                                                    \
+    for (int i = 0; i < 12; ++i) g.v[i] *= inv_gs;                                   \
+    if (base_at) {                                                                   \
+_Pragma("unroll")                                                                    \
+        for (int i = 0; i < 12; ++i) g.v[i] = fmaf(br.v[i], inv_gs, g.v[i]);         \
+    } else if (base) {                                                               \
+_Pragma("unroll")                                                                    \
+        for (int i = 0; i < 12; ++i) g.v[i] += br.v[i];                              \
+    }                                                                                \
+    if (TAP) {                                                                       \
+_Pragma("unroll")                                                                    \
+        for (int i = 0; i < 12; ++i) g.v[i] += tr.v[i];                              \
+    }                                                                                \
+    if (dx) g.store(dx + (size_t)row * D, lane);                                     \
+    if (out3) g.store_split3(out3 + (size_t)row * SPLIT_A * D, lane, s3, hi3 != 0);  \
+    if (g_at) {                                                                      \
+        Row12 gsc;                                                                   \
+_Pragma("unroll")                                                                    \
+        for (int i = 0; i < 12; ++i) gsc.v[i] = g.v[i] * gs;                         \
+        gsc.store(g_at + (size_t)row * D, lane);                                     \
+    }                                                                                \
+    if (dmask_next) {                                                                \
+        float dm = 0.f;                                                              \
+        if (h_next && r >= 0) {                                                      \
+            Row12 hr;                                                                \
+            hr.load_at(h_next + (size_t)r * D, lane);                                \
+            LN_ROWPIN(hr);                                                           \
+            dm = dot12(g, hr);                                                       \
+        }                                                                            \
+        if (lane == 0) dmask_next[row] = dm;                                         \
+    }
 template <class AT>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const AT* __restrict__ dy, const float* __restrict__ x,
                                                      const float2* __restrict__ stats, const float* __restrict__ w,
@@ -60,51 +117,47 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const AT* __restrict__ dy, 
                                                      const int* __restrict__ dst_of_next, float* __restrict__ dmask_next,
                                                      float gs, float inv_gs, bf16* __restrict__ out3, float s3, int hi3,
                                                      const AT* __restrict__ base_at) {
+    constexpr const float* tap = nullptr;   // (named by the body's TAP branches, which are not compiled in here)
+    LN_BWD_BODY(false)
+}
+template <class AT>
+__global__ __launch_bounds__(256) void ln_bwd_tap_kernel(const AT* __restrict__ dy, const float* __restrict__ x,
+                                                         const float2* __restrict__ stats, const float* __restrict__ w,
+                                                         const float* __restrict__ base, float* __restrict__ dx, int rows,
+                                                         AT* __restrict__ g_at, const AT* __restrict__ h_next,
+                                                         const int* __restrict__ dst_of_next, float* __restrict__ dmask_next,
+                                                         float gs, float inv_gs, bf16* __restrict__ out3, float s3, int hi3,
+                                                         const AT* __restrict__ base_at, const float* __restrict__ tap) {
+    LN_BWD_BODY(true)
+}
+
+// (mean, rstd) of every row alone: the final norm's statistics over all 197 rows of an image, which no forward pass keeps (the head
+// normalises the cls row only) -- dyt_backward_tokens recomputes them in front of the final norm's backward
+__global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, float2* __restrict__ stats, int rows) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    // every load of the row is issued up front and completed by ONE full drain that names all of them (DYT_PIN*, dyt_common.h)
-    // base_at (round 6, fp16 mode): the gradient stream this row's LayerNorm gradient is added to arrives as the 16-bit, gs-scaled copy the
-    // kernel before wrote for its GEMM (tok_bwd's du_at) instead of as an fp32 [M,768] stream; dx == null: no fp32 copy is written either
-    Row12 g, xr, wr, br;
-    g.load_at(dy + (size_t)row * D, lane);
-    xr.load_nt(x + (size_t)row * D, lane);   // residual snapshot of the forward pass: last use
-    wr.load(w, lane);
-    float2 st = stats[row];
-    int r = dst_of_next ? dst_of_next[row] : row;
-    if (base_at) br.load_at(base_at + (size_t)row * D, lane);
-    else if (base) br.load(base + (size_t)row * D, lane);
-    LN_ROWPIN(g); LN_ROWPIN(xr); LN_ROWPIN(wr);
-    LN_SCALPIN3(st.x, st.y, r);
-    if (base || base_at) LN_ROWPIN(br);
-    ln_bwd_row(g, xr, wr, st);
+    Row12 xr;
+    xr.load(x + (size_t)row * D, lane);
+    xr.landed();
+    const float2 st = ln_stats(xr);
+    if (lane == 0) stats[row] = st;
+}
+// out = a + b (b null: a copy): the top of the gradient stream where the final norm is an identity, or where only the top tap has a gradient
+__global__ __launch_bounds__(256) void rows_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int rows) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    Row12 ar, br;
+    ar.load(a + (size_t)row * D, lane);
+    if (b) br.load(b + (size_t)row * D, lane);
+    ar.landed();
+    if (b) {
+        br.landed();
 #pragma unroll
-    for (int i = 0; i < 12; ++i) g.v[i] *= inv_gs;   // dy carried the 16-bit gradient factor (1 in the bf16 / fp32 builds: exact)
-    if (base_at) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) g.v[i] = fmaf(br.v[i], inv_gs, g.v[i]);
-    } else if (base) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) g.v[i] += br.v[i];
+        for (int i = 0; i < 12; ++i) ar.v[i] += br.v[i];
     }
-    if (dx) g.store(dx + (size_t)row * D, lane);
-    if (out3) g.store_split3(out3 + (size_t)row * SPLIT_A * D, lane, s3, hi3 != 0);   // fp32 split form: the next block's GELU' dgrad operand
-    if (g_at) {
-        Row12 gsc;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) gsc.v[i] = g.v[i] * gs;
-        gsc.store(g_at + (size_t)row * D, lane);
-    }
-    if (dmask_next) {
-        float dm = 0.f;
-        if (h_next && r >= 0) {
-            Row12 hr;
-            hr.load_at(h_next + (size_t)r * D, lane);
-            LN_ROWPIN(hr);
-            dm = dot12(g, hr);
-        }
-        if (lane == 0) dmask_next[row] = dm;
-    }
+    ar.store(out + (size_t)row * D, lane);
 }
 
 int launch_ln_fwd(int precision, const float* x, const float* w, const float* b, void* out, float2* stats, int rows,
@@ -123,14 +176,35 @@ int launch_ln_fwd_f32out(const float* x, const float* w, const float* b, float* 
 }
 int launch_ln_bwd(int precision, const void* dy, const float* x, const float2* stats, const float* w, const float* base,
                   float* dx, int rows, void* g_at, const void* h_next, const int* dst_of_next, float* dmask_next,
-                  float gs, hipStream_t s, void* out3, float s3, int out3_hi_only, const void* base_at) {
+                  float gs, hipStream_t s, void* out3, float s3, int out3_hi_only, const void* base_at, const float* tap) {
     if (dbg_skip(16)) return 0;
+    if (tap) {   // the tapped instantiations (dyt_backward_tokens); everything else launches the kernels it always did
+        if (precision == 0)
+            hipLaunchKernelGGL(ln_bwd_tap_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)dy, x, stats, w, base, dx,
+                               rows, (float*)g_at, (const float*)h_next, dst_of_next, dmask_next, 1.0f, 1.0f, (bf16*)out3, s3, out3_hi_only, (const float*)nullptr, tap);
+        else
+            hipLaunchKernelGGL(ln_bwd_tap_kernel<bf16>, dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16*)dy, x, stats, w, base, dx,
+                               rows, (bf16*)g_at, (const bf16*)h_next, dst_of_next, dmask_next, gs, 1.0f / gs, (bf16*)nullptr, 1.0f, 0, (const bf16*)base_at, tap);
+        LAUNCH_CHECK();
+        return 0;
+    }
     if (precision == 0)
         hipLaunchKernelGGL(ln_bwd_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)dy, x, stats, w, base, dx,
                            rows, (float*)g_at, (const float*)h_next, dst_of_next, dmask_next, 1.0f, 1.0f, (bf16*)out3, s3, out3_hi_only, (const float*)nullptr);
     else
         hipLaunchKernelGGL(ln_bwd_kernel<bf16>, dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16*)dy, x, stats, w, base, dx,
                            rows, (bf16*)g_at, (const bf16*)h_next, dst_of_next, dmask_next, gs, 1.0f / gs, (bf16*)nullptr, 1.0f, 0, (const bf16*)base_at);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_ln_stats(const float* x, float2* stats, int rows, hipStream_t s) {
+    hipLaunchKernelGGL(ln_stats_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, stats, rows);
+    LAUNCH_CHECK();
+    return 0;
+}
+int launch_rows_add(const float* a, const float* b, float* out, int rows, hipStream_t s) {
+    hipLaunchKernelGGL(rows_add_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, a, b, out, rows);
     LAUNCH_CHECK();
     return 0;
 }

@@ -550,6 +550,24 @@ extern "C" int dyt_unit_ln_bwd(const void* dy, const float* x, const float* stat
     return DYT_OK;
 }
 
+extern "C" int dyt_unit_ln_bwd_tap(const void* dy, const float* x, const float* stats, const float* w, const float* base, const void* base_at,
+                                   float* dx, int rows, void* g_at, const void* h_next, const int32_t* dst_of_next, float* dmask_next, float gs,
+                                   void* out3, float s3, int out3_hi_only, const float* tap, int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_ln_bwd_tap", precision); if (rc) return rc; }
+    if (!dy || !x || !stats || !w || !tap || rows < 1) { set_error("dyt_unit_ln_bwd_tap: dy / x / stats / w / tap is NULL or rows = %d < 1", rows); return DYT_ERR_ARG; }
+    if (!dx && !g_at && !out3) { set_error("dyt_unit_ln_bwd_tap: no output row (dx, g_at and out3 are all NULL)"); return DYT_ERR_ARG; }
+    if (out3 && precision != 0) { set_error("dyt_unit_ln_bwd_tap: out3 (the split operand) exists at precision 0 only"); return DYT_ERR_ARG; }
+    if (base_at && precision == 0) { set_error("dyt_unit_ln_bwd_tap: base_at (the 16-bit stream) exists at precision 1 only"); return DYT_ERR_ARG; }
+    if (base && base_at) { set_error("dyt_unit_ln_bwd_tap: base and base_at are alternatives"); return DYT_ERR_ARG; }
+    if (!(gs > 0.f)) { set_error("dyt_unit_ln_bwd_tap: gs = %g (> 0)", gs); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_ln_bwd(precision, dy, x, reinterpret_cast<const float2*>(stats), w, base, dx, rows, g_at, h_next, dst_of_next, dmask_next, gs, s,
+                           out3, s3, out3_hi_only, base_at, tap);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
 extern "C" int dyt_unit_ln_param_grad(const void* dy, const float* x, const float* stats, float* out, int rows, float gs, int precision,
                                       void* stream) {
     { int rc = unit_precision_ok("dyt_unit_ln_param_grad", precision); if (rc) return rc; }

@@ -181,6 +181,54 @@ class _DyTFunction(torch.autograd.Function):
         return (None,) * 7 + grads
 
 
+class _DyTFeaturesFunction(torch.autograd.Function):
+    """Autograd bridge of ``forward_features``: forward = dyt_forward_taps (a token-level pass saved inside the library, slot 0 = student /
+    1 = complete_model pass), backward = dyt_backward_tokens -> gradients of the adapters, gates, adapter LayerNorms and scales.  The
+    head is not part of this route: ``head.*`` / ``fc_norm.*`` get None."""
+
+    @staticmethod
+    def forward(ctx, model, x, complete_model, g1, g2, keep_mask, seed, out_indices, *params):
+        eng = model._engine
+        slot = 1 if complete_model else 0
+        res = eng.forward_features_tokens(x, training=model.training, complete_model=complete_model, save=True,
+                                          masked_dense=(model.training and model.train_mode == "masked"), g1=g1, g2=g2, keep_mask=keep_mask,
+                                          seed=seed, taps=out_indices, slot=slot)   # (the flags of the forward-only route + DYT_F_SAVE: the same values)
+        tok, taps, ts, tl = res if out_indices else (res[0], (), res[1], res[2])
+        out = tok if model.use_fc_norm else model._final_norm(tok)   # (the final norm's backward runs inside dyt_backward_tokens)
+        ctx.model, ctx.slot, ctx.out_indices = model, slot, tuple(out_indices or ())
+        ctx.engine, ctx.generation = eng, eng.generation[slot]
+        ctx.set_materialize_grads(False)
+        return (out, ts, tl) + tuple(taps)
+
+    @staticmethod
+    def backward(ctx, dtokens, dts, dtl, *dtaps):
+        model = ctx.model
+        eng = model._engine
+        if eng is not ctx.engine or eng.generation[ctx.slot] != ctx.generation:
+            # activations are saved inside the library, ONE set per kind of pass (slot 0 student, slot 1 complete_model)
+            raise DyTError("backward through a %s forward whose saved activations were overwritten by a later forward of "
+                           "the same kind (or the engine was re-created): run backward before the next such forward"
+                           % ("complete_model" if ctx.slot else "student"))
+        gbuf = torch.zeros_like(eng.flat)
+        n = len(model._trainables)
+        if dtokens is None and dts is None and dtl is None and all(d is None for d in dtaps):
+            return (None,) * (8 + n)
+        per_block = [None] * eng.depth
+        for i, d in zip(ctx.out_indices, dtaps):
+            per_block[i] = None if d is None else d.float().contiguous()
+        eng.backward_tokens(ctx.slot, None if dtokens is None else dtokens.float().contiguous(), per_block, gbuf,
+                            dtoken_select=None if dts is None else dts.float().contiguous(),
+                            dtoken_logits=None if dtl is None else dtl.float().contiguous())
+        grads = tuple(eng.trainable_view(name, p.shape, gbuf) if p.requires_grad and not _head_side(name) else None
+                      for name, p in model._trainables)
+        return (None,) * 8 + grads
+
+
+def _head_side(name):
+    """Trainable tensors behind the tokens: no gradient reaches them through forward_features."""
+    return name.startswith("head.") or name.startswith("fc_norm.")
+
+
 class VisionTransformer(nn.Module):
     """DyT ViT-B/16 (reference :192-385)."""
 
@@ -403,18 +451,38 @@ class VisionTransformer(nn.Module):
                                          keep_mask=keep_mask, seed=seed)
         return logits, dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))
 
-    @torch.no_grad()
-    def forward_features(self, x, complete_model=False, gumbel=None, keep_mask=None):
+    def _final_norm(self, tok):
+        """The frozen final LayerNorm on every token row, through the C ABI's ``dyt_layernorm``."""
+        from _lib import check, lib, ptr, stream_ptr
+        out = torch.empty_like(tok)
+        check(lib().dyt_layernorm(ptr(tok.view(-1, self.embed_dim)), ptr(self.norm.weight.detach().float().contiguous()),
+                                  ptr(self.norm.bias.detach().float().contiguous()), ptr(out.view(-1, self.embed_dim)),
+                                  tok.shape[0] * tok.shape[1], stream_ptr()))
+        return out
+
+    def forward_features(self, x, complete_model=False, gumbel=None, keep_mask=None, out_indices=None):
         """Reference :343-371: the block stack's output after the final norm, ``(tokens [B,197,768], {"token_select", "token_logits"})``
         (with fc_norm the final norm is an identity, :314: the un-normalised tokens).
         Runs the same HIP forward with DYT_F_TOKENS_OUT (every token of the last block is then computed: no cls-only tail) and the final
-        LayerNorm through the C ABI's ``dyt_layernorm``.  Forward only -- training goes through ``forward`` / the fused step."""
-        import ctypes
-        from _lib import check, lib, ptr, stream_ptr
+        LayerNorm through the C ABI's ``dyt_layernorm``.
+
+        ``out_indices`` (distinct block indices in [0, depth), negative values count from the end): the return value is
+        ``(tokens, taps, aux)`` with ``taps`` a tuple of [B,197,768] tensors in the order given, the residual stream behind each of those
+        blocks with no final norm -- what the reference's dense-prediction backbone returns for ``out_indices=[3, 5, 7, 11]``
+        (dense_tasks/Segmentation/backbone/segmentation_vision_transformer_IN21K.py:526-560) before it reshapes to maps.
+
+        Differentiable: with grad enabled and a trainable parameter requiring grad, tokens, taps and aux carry gradients to the adapters,
+        the gates, the adapter LayerNorms and the learnable scale (dyt_backward_tokens); the head and ``fc_norm`` are behind the tokens and
+        get none, the final ``norm`` is frozen.  The caller owns head, loss and optimizer.  Under ``torch.no_grad()``, in inference-only
+        models, and in eval() mode without ``out_indices`` (the call as it was before it became differentiable: the same bits) it is the
+        forward alone; an eval-mode model is differentiated by naming ``out_indices``."""
+        from _lib import check_out_indices
         if not x.is_cuda:
             raise DyTError("DyT VisionTransformer runs on a HIP device only (input is on %s); there is no CPU path" % x.device)
         if self._frames and self._frames > 1:
             raise NotImplementedError("forward_features of the video model: its head pools every frame's tokens inside the fused forward")
+        if out_indices is not None:
+            out_indices = check_out_indices(out_indices, self.depth)
         self._refuse_training("forward_features", grad_check=False)
         x = self.prepare_input(x)
         eng = self.engine(x.shape[0], x.device)
@@ -425,15 +493,27 @@ class VisionTransformer(nn.Module):
             keep_mask = keep_mask.to(x.device, torch.uint8).contiguous()
         self._seed_counter += 1
         seed = (torch.initial_seed() * 1000003 + self._seed_counter) & (2 ** 63 - 1)
-        tok, ts, tl = eng.forward_features_tokens(x, training=self.training, complete_model=bool(complete_model),
-                                                  masked_dense=(self.training and self.train_mode == "masked"), g1=g1, g2=g2, keep_mask=keep_mask, seed=seed)
-        if self.use_fc_norm:
-            return tok, dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))
-        out = torch.empty_like(tok)
-        check(lib().dyt_layernorm(ptr(tok.view(-1, self.embed_dim)), ptr(self.norm.weight.detach().float().contiguous()),
-                                  ptr(self.norm.bias.detach().float().contiguous()), ptr(out.view(-1, self.embed_dim)),
-                                  tok.shape[0] * tok.shape[1], stream_ptr()))
-        return out, dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))
+        # (an eval-mode call without out_indices predates the differentiable route and keeps what it had: the forward alone, the same bits --
+        # a saved pass of the 16-bit modes is not the unsaved one bit for bit)
+        need_grad = (not self.inference_only and torch.is_grad_enabled() and (self.training or out_indices is not None)
+                     and any(p.requires_grad for n, p in self._trainables if not _head_side(n)))
+        if need_grad:
+            if not self.use_fc_norm and any(p.requires_grad for p in self.norm.parameters()):
+                raise NotImplementedError("norm.requires_grad=True: forward_features trains exactly the reference's freeze rule (adapters, gates; the final "
+                                          "norm is frozen -- main_image.py:250-256); --fulltune / partial freezing is not supported")
+            res = _DyTFeaturesFunction.apply(self, x, bool(complete_model), g1, g2, keep_mask, seed, out_indices,
+                                             *[p for _, p in self._trainables])
+            out, ts, tl, taps = res[0], res[1], res[2], tuple(res[3:])
+        else:
+            res = eng.forward_features_tokens(x, training=self.training, complete_model=bool(complete_model),
+                                              masked_dense=(self.training and self.train_mode == "masked"), g1=g1, g2=g2, keep_mask=keep_mask,
+                                              seed=seed, taps=out_indices)
+            tok, taps, ts, tl = res if out_indices is not None else (res[0], (), res[1], res[2])
+            out = tok if self.use_fc_norm else self._final_norm(tok)
+        aux = dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))
+        if out_indices is None:
+            return out, aux
+        return out, taps, aux
 
     @torch.no_grad()
     def forward_head(self, x, pre_logits: bool = False):

@@ -11,7 +11,7 @@ import torch
 
 from _lib import (CREATE_AVG_POOL, CREATE_FC_NORM, CREATE_WIDE_HEAD, Config, DyTError, F_ACCUM_GRAD, F_COMPLETE, F_DEVICE_SEED, F_GATE_ALWAYS, F_MASKED_DENSE, F_SAVE, F_TOKENS_IN, F_TOKENS_OUT,
                   F_TRAINING, F_IMAGES_NHWC, F_IMAGES_U8, OPT_F32_SPLIT16, OPT_LEARNABLE_SCALE, PREC_BF16, PREC_FP16, PREC_FP16X3, PREC_FP16F8, PREC_FP16X3F, PREC_FP16X3H, PREC_FP16X3Q, PREC_FP32,
-                  INPUT_NORMS, adamw_segment_array, byte_image_layout, check, float3, is_trainable_param, key_to_param, lib, ptr, stream_ptr)
+                  INPUT_NORMS, adamw_segment_array, byte_image_layout, check, float3, is_trainable_param, key_to_param, lib, ptr, ptr_array, stream_ptr)
 
 NP, NT, DIM = 196, 197, 768
 
@@ -224,22 +224,53 @@ class DyTEngine:
                                      ctypes.c_uint64(seed & (2 ** 64 - 1)), ptr(out), ptr(ts), ptr(tl), stream_ptr()))
         return out, ts, tl
 
-    def forward_features_tokens(self, images, training=False, complete_model=False, masked_dense=False, g1=None, g2=None, keep_mask=None, seed=0):
+    def forward_features_tokens(self, images, training=False, complete_model=False, masked_dense=False, g1=None, g2=None, keep_mask=None, seed=0,
+                                save=False, taps=None, slot=0):
         """Images in, the block stack's output tokens out (DYT_F_TOKENS_OUT without DYT_F_TOKENS_IN): what the reference's forward_features
-        holds right before its final norm (vision_transformer_IN21K.py:343-368).  Forward only.  Returns (tokens [B,197,768],
-        token_select [B,depth,196], token_logits [B,depth,196])."""
+        holds right before its final norm (vision_transformer_IN21K.py:343-368).  Returns (tokens [B,197,768],
+        token_select [B,depth,196], token_logits [B,depth,196]).
+
+        ``taps``: block indices in [0, depth) -- the residual stream behind each of those blocks, un-normalised, is returned as well
+        (dyt_forward_taps): ``(tokens, taps, token_select, token_logits)`` with ``taps`` a tuple of [B,197,768] tensors in the order given.
+        ``save=True`` keeps the pass in ``slot`` for ``backward_tokens``."""
         B = images.shape[0]
         flags = ((F_TRAINING if training else 0) | (F_COMPLETE if complete_model else 0) | (F_MASKED_DENSE if masked_dense else 0) |
-                 F_GATE_ALWAYS | F_TOKENS_OUT | self._image_flags(images))
+                 (F_SAVE if save else 0) | F_GATE_ALWAYS | F_TOKENS_OUT | self._image_flags(images))
         if training:
-            self._dp_check((0,), B)
+            self._dp_check((slot,), B)
         out = torch.empty(B, NT, DIM, device=self.device, dtype=torch.float32)
         ts = torch.zeros(B, self.depth, NP, device=self.device, dtype=torch.float32)
         tl = torch.zeros(B, self.depth, NP, device=self.device, dtype=torch.float32)
+        if taps is None and not save:
+            with torch.cuda.device(self.device):
+                self._ck(self.L.dyt_forward(self.h, slot, ptr(images), B, flags, ptr(self.flat), ptr(g1), ptr(g2), ptr(keep_mask),
+                                         ctypes.c_uint64(seed & (2 ** 64 - 1)), ptr(out), ptr(ts), ptr(tl), stream_ptr()))
+            return out, ts, tl
+        if not hasattr(self.L, "dyt_forward_taps"):
+            raise DyTError("this libdyt_hip has no dyt_forward_taps (token-level training, taps): rebuild it")
+        bufs = [None] * self.depth
+        for i in (taps or ()):
+            bufs[i] = torch.empty(B, NT, DIM, device=self.device, dtype=torch.float32)
+        if save:
+            self.generation[slot] += 1
         with torch.cuda.device(self.device):
-            self._ck(self.L.dyt_forward(self.h, 0, ptr(images), B, flags, ptr(self.flat), ptr(g1), ptr(g2), ptr(keep_mask),
-                                     ctypes.c_uint64(seed & (2 ** 64 - 1)), ptr(out), ptr(ts), ptr(tl), stream_ptr()))
-        return out, ts, tl
+            self._ck(self.L.dyt_forward_taps(self.h, slot, ptr(images), B, flags, ptr(self.flat), ptr(g1), ptr(g2), ptr(keep_mask),
+                                             ctypes.c_uint64(seed & (2 ** 64 - 1)), ptr(out), ptr_array(bufs, self.depth), ptr(ts), ptr(tl),
+                                             stream_ptr()))
+        if taps is None:
+            return out, ts, tl
+        return out, tuple(bufs[i] for i in taps), ts, tl
+
+    def backward_tokens(self, slot, dtokens, dtaps, grad, dtoken_select=None, dtoken_logits=None, dtok=None):
+        """dyt_backward_tokens: the backward of a pass saved by ``forward_features_tokens(save=True)``.  ``dtokens`` [B,197,768] or None: the
+        gradient of the final norm's output (fc_norm engines: of the tokens); ``dtaps``: None or ``depth`` entries, each None or the
+        [B,197,768] gradient of that block's tap.  Adapter / gate / adapter-LayerNorm / scale gradients accumulate into ``grad``; the
+        head's ranges are left alone.  There is no captured-graph form of this route."""
+        if not hasattr(self.L, "dyt_backward_tokens"):
+            raise DyTError("this libdyt_hip has no dyt_backward_tokens (token-level training): rebuild it")
+        with torch.cuda.device(self.device):
+            self._ck(self.L.dyt_backward_tokens(self.h, slot, ptr(dtokens), ptr_array(dtaps, self.depth), ptr(dtoken_select), ptr(dtok),
+                                                ptr(dtoken_logits), ptr(grad), stream_ptr()))
 
     def backward(self, slot, dlogits, grad, dtoken_select=None, dtok=None, dtoken_logits=None):
         with torch.cuda.device(self.device):

@@ -362,6 +362,32 @@ int dyt_forward(dyt_ctx* ctx, int slot, const float* images, int batch, int flag
 int dyt_backward(dyt_ctx* ctx, int slot, const float* dlogits, const float* dtoken_select,
                  const float* dtok_uniform, const float* dtoken_logits, float* grad_flat, void* stream);
 
+/* Token-level training: the backbone under a head and a loss of the caller's own (a dense-prediction head over the reference backbone's
+ * out_indices, dense_tasks/Segmentation/backbone/segmentation_vision_transformer_IN21K.py:526-560).  Image model (frames = 1) only.
+ *
+ * dyt_forward_taps: dyt_forward with DYT_F_TOKENS_OUT and without DYT_F_TOKENS_IN (`tokens` [B,197,768] takes the place of `logits`:
+ * the last block's output, no final norm), which also writes taps[i] -- an array of `depth` DEVICE pointers in HOST memory, each NULL or an
+ * fp32 [B,197,768] buffer -- := the residual stream behind block i, un-normalised, on `stream`: bit for bit the pass's own snapshot
+ * xs[i + 1]; no other output bit of the pass depends on `taps` (NULL: none).  Inference-only contexts serve it too.  With DYT_F_SAVE
+ * the slot holds a TOKEN-LEVEL pass: every row of the last block is saved, dyt_backward_tokens is its backward, dyt_backward refuses it
+ * (as dyt_backward_tokens refuses a slot saved by dyt_forward without DYT_F_TOKENS_OUT).
+ *
+ * dyt_backward_tokens: gradients of the adapters, gates, adapter LayerNorms and learnable scales ACCUMULATED into grad_flat exactly as
+ * dyt_backward does; the ranges of head.*, fc_norm.* (and the frozen norm.*) are left as they are.
+ *   dtokens        [B,197,768] fp32 or NULL: gradient of LN_final(tokens) (contexts with DYT_CREATE_FC_NORM, whose final norm is an
+ *                  identity: of the tokens themselves)
+ *   dtaps          NULL or an array of `depth` device pointers in host memory, each NULL or the fp32 [B,197,768] gradient of taps[i]
+ *   dtoken_select / dtok_uniform / dtoken_logits   as dyt_backward
+ * All adds happen in the library: the top of the stream is LNbwd_final(dtokens) + dtaps[depth-1]; dtaps[i], i < depth-1, is added in fp32
+ * inside block i+1's LayerNorm-1 backward, in front of every store and rounding of that row.
+ * DYT_ERR_ARG / DYT_ERR_STATE with a text, before anything is enqueued: every gradient input NULL, frames > 1, an inference-only context,
+ * a slot that does not hold a token-level pass.  Not part of dyt_step_fwd_bwd, so there is no captured-graph form of this route. */
+int dyt_forward_taps(dyt_ctx* ctx, int slot, const float* images, int batch, int flags, const float* trainable,
+                     const float* gumbel_g1, const float* gumbel_g2, const uint8_t* keep_mask, uint64_t seed,
+                     float* tokens, float* const* taps, float* token_select, float* token_logits, void* stream);
+int dyt_backward_tokens(dyt_ctx* ctx, int slot, const float* dtokens, const float* const* dtaps, const float* dtoken_select,
+                        const float* dtok_uniform, const float* dtoken_logits, float* grad_flat, void* stream);
+
 /* Loss of the fine-tune step and its gradient w.r.t. both logits -- engine_finetune.py:52-63 and
  * AdaLoss.forward models/losses.py:48-84:
  *   loss = CE(s,y) + ratio*((mean(mask)-target)^2 + w_min*sum(clamp(t_min-mask,0))) + CE(t,y)
@@ -644,6 +670,11 @@ int dyt_unit_bwd_prep(const float* g, const void* h, const int32_t* dst_of, cons
 int dyt_unit_ln_bwd(const void* dy, const float* x, const float* stats, const float* w, const float* base, const void* base_at, float* dx,
                     int rows, void* g_at, const void* h_next, const int32_t* dst_of_next, float* dmask_next, float gs, void* out3,
                     float s3, int out3_hi_only, int precision, void* stream);
+/* the tapped instantiations of the same kernel (dyt_backward_tokens): d as above + tap[row], tap fp32 [rows][768], not NULL; added in
+ * fp32 behind base / base_at and in front of every output */
+int dyt_unit_ln_bwd_tap(const void* dy, const float* x, const float* stats, const float* w, const float* base, const void* base_at, float* dx,
+                        int rows, void* g_at, const void* h_next, const int32_t* dst_of_next, float* dmask_next, float gs, void* out3,
+                        float s3, int out3_hi_only, const float* tap, int precision, void* stream);
 /* ln_param_grad_kernel + ln_param_reduce_kernel (launch_ln_param_grad; scratch allocated inside): out[0:768] += sum_t (dy[t] / gs) xhat[t],
  * out[768:1536] += sum_t dy[t] / gs, xhat = (x - mean) rstd from `stats`. */
 int dyt_unit_ln_param_grad(const void* dy, const float* x, const float* stats, float* out, int rows, float gs, int precision, void* stream);
