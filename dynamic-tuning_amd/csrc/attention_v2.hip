@@ -1,14 +1,14 @@
-// Round-5 attention kernels for the 16-bit modes (N = 197 tokens, 12 heads x 64): the same math as attention.hip
+// Round-5 attention kernels for the 16-bit modes (N = 197 tokens, 12 heads x 64): the same math as attention_16.hip
 // (Attention.forward of the reference, models/vision_transformer_IN21K.py:60-70, and its autograd backward), restructured:
 //   * ONE LDS image per operand.  K / V (forward) and Q / dO / K / V (backward) are row-major [224][64] 16-bit images filled by
 //     LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write pass, no VALU); the 16-byte chunks of a row are XOR-swizzled
 //     on the DMA *source* address (the DMA destination is lane-linear) so that both kinds of fragment reads are bank-conflict free:
 //       row fragments        (MFMA operand = 8 consecutive channels of one row)   ds_read_b128
 //       transposed fragments (MFMA operand = 4 + 4 consecutive ROWS of one channel) ds_read_b64_tr_b16 straight from the same image
-//     -- the transposed LDS copies of attention.hip (and their 4-way conflicting ds_write_b32 scatter) are gone.
+//     -- the transposed LDS copies of attention_16.hip (and their 4-way conflicting ds_write_b32 scatter) are gone.
 //   * forward: online softmax per 32-key tile (running max / sum, the rescale deferred until the max grows by more than 2^THR), so a
 //     wave holds ONE score tile instead of seven: <= 128 VGPRs, 57 KB of LDS -> two 7-wave workgroups per CU whose load / MFMA / VALU
-//     phases interleave (attention.hip: one workgroup per CU, every wave in the same phase).
+//     phases interleave (attention_16.hip: one workgroup per CU, every wave in the same phase).
 #include "kernels.h"
 
 namespace dyt {
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v2_kernel(const bf16* __restr
 // ------------------------------------------------------------------------------------------
 // backward: dQ, dK, dV of one (image, head) in one persistent workgroup pass
 // ------------------------------------------------------------------------------------------
-// The arithmetic of attention.hip's fused kernel (phase B: wave w owns KEY tile w and walks the query tiles -> dK, dV; phase A: wave w
+// The arithmetic of attention_16.hip's fused kernel (phase B: wave w owns KEY tile w and walks the query tiles -> dK, dV; phase A: wave w
 // owns QUERY tile w and walks the key tiles -> dQ; S and dP are recomputed in both), on a different data path:
 //   * Q, dO, K, V are four swizzled LDS images filled by LDS-DMA; every transposed operand (dO^T, Q^T, K^T) is a ds_read_b64_tr_b16 of
 //     the same image -- no register staging, no transposed copies, no re-staging between the phases;

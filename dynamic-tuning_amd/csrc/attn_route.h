@@ -1,6 +1,6 @@
 // Which kernel an attention launch gets: two pure functions of the few properties of the call and of the process-wide switches the
 // decision reads.  No HIP here: attention.hip fills a shape (copying the switches in), refuses with the route's error, and switches over
-// the kernel id; tools/attn_route_check.cpp walks the same functions on the CPU (tests/test_attn_route_host.py).
+// the kernel id to the family unit that launches it (attention_16.hip, attention_exact.hip, attention_split.hip, attention_v2.hip); tools/attn_route_check.cpp walks the same functions on the CPU (tests/test_attn_route_host.py).
 #pragma once
 
 namespace dyt {

@@ -157,7 +157,8 @@ struct AttnBwdArgs {
 };
 int launch_attn_fwd(int precision, const AttnFwdArgs& a, hipStream_t s);
 int launch_attn_bwd(int precision, const AttnBwdArgs& a, hipStream_t s);
-// the round-5 kernels' side of the two launchers above (attention_v2.hip): r.kernel is one of AF_V2* / the route is AB_V2
+// the round-5 kernels' side of the two launchers above (attention_v2.hip): r.kernel is one of AF_V2* / the route is AB_V2; the other
+// families' entries of the same shape are declared in attn_common.h
 int launch_attn_fwd_v2(const AttnFwdArgs& a, const AttnFwdRoute& r, hipStream_t s);
 int launch_attn_bwd_v2(const AttnBwdArgs& a, hipStream_t s);
 // process-wide switches (attention.hip: AttnSwitches)

@@ -764,7 +764,7 @@ extern "C" int dyt_unit_pad_convert(const float* src, void* dst, int rows, int c
     return DYT_OK;
 }
 
-// ---- the attention kernels alone (attention.hip, attention_v2.hip): the structs are AttnFwdArgs / AttnBwdArgs of kernels.h field for field, the
+// ---- the attention kernels alone (attention.hip and its family units attention_{16,exact,split,v2}.hip): the structs are AttnFwdArgs / AttnBwdArgs of kernels.h field for field, the
 // ---- kernel is whatever attn_fwd_route() / attn_bwd_route() pick from them and the three process-wide switches.  The launcher's own checks
 // ---- refuse a bad call; no arithmetic, no kernels, no layout conversion here.  Test-only (tests/test_gpu_unit_attention.py). ----
 extern "C" int dyt_unit_attn_fwd(const dyt_unit_attn_fwd_args* p, int precision, void* stream) {

@@ -271,7 +271,7 @@ int dyt_ctx_bytes(const dyt_ctx* ctx, int64_t* bytes);
  *                           wave, V^T fragments by ds_read_b64_tr_b16 from the row-major image, online softmax per 32-key tile), bit 1 = the
  *                           round-5 BACKWARD kernel (four DMA images, every transposed operand a transposed read of the same image, row
  *                           statistics by the loader wave, results stored as whole rows from inside the next tile loop).  0: the round 1-4
- *                           kernels of csrc/attention.hip (DYT_OPT_ATTN_BWD_FUSED then selects among those).  Same arithmetic contract;
+ *                           kernels of csrc/attention_16.hip (DYT_OPT_ATTN_BWD_FUSED then selects among those).  Same arithmetic contract;
  *                           different summation order, so results agree to rounding, not bit for bit.  PROCESS-wide. */
 #define DYT_OPT_ATTN_V2 9
 /*   DYT_OPT_GEMM_SPLITK         default 1 (environment DYT_SPLITK overrides the default).  16-bit kernels: the K = 3072 GEMMs of the cls-only
@@ -758,7 +758,7 @@ int dyt_unit_embed(const float* images, void* patches, const float* cls, const f
  * (launch_transpose_convert), rounded to the operand type, zero outside the source. */
 int dyt_unit_pad_convert(const float* src, void* dst, int rows, int cols, int dst_rows, int dst_cols, int transpose, int precision, void* stream);
 
-/* ---- the attention kernels alone (csrc/attention.hip, csrc/attention_v2.hip), for tests/test_gpu_unit_attention.py.  The structs mirror
+/* ---- the attention kernels alone (csrc/attention.hip and the family units csrc/attention_{16,exact,split,v2}.hip), for tests/test_gpu_unit_attention.py.  The structs mirror
  * AttnFwdArgs / AttnBwdArgs of csrc/kernels.h field for field (bool as int32); unset pointers are NULL.  The entries check the struct
  * pointer, `precision` and batch >= 1, call launch_attn_fwd / launch_attn_bwd, return the launcher's error (every refusal of
  * csrc/attn_route.h and of the launchers arrives as DYT_ERR_ARG with a text, before anything is enqueued) and synchronise: no arithmetic,

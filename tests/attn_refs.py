@@ -1,4 +1,4 @@
-"""Plain-torch CPU references of the attention kernels (csrc/attention.hip, csrc/attention_v2.hip), for tests/test_gpu_unit_attention.py.
+"""Plain-torch CPU references of the attention kernels (csrc/attention_16.hip, attention_exact.hip, attention_split.hip, attention_v2.hip), for tests/test_gpu_unit_attention.py.
 
 Every tensor here is in the kernels' head layout: q / k / v / out / dout / dq / dk / dv [H = B*12][197][64], q already times 1/8, lse / delta
 [H][197]; ``to_tokens`` / ``to_heads`` move between that and the [B*197][768] token rows of `out` / `dout` / `dqkv`.  Every function takes
@@ -166,7 +166,7 @@ def share(got, ref64, A):
 # ---- a 16-bit kernel on the CPU --------------------------------------------------------------------------------------------------
 def emulate_fwd16(q, k, v, dt, leak_pad=False, drop_last=False):
     """The arithmetic of the 16-bit forward kernels in fp32 with their roundings: scores and the row sum in fp32, P rounded to dt before P v
-    (attention.hip `pack8(st[kt], ..)`, attention_v2.hip `pack8(s, ..)`), out = (P16 v) / sum rounded to dt by the store; (out dt, lse fp32).
+    (attention_16.hip `pack8(st[kt], ..)`, attention_v2.hip `pack8(s, ..)`), out = (P16 v) / sum rounded to dt by the store; (out dt, lse fp32).
     leak_pad: the 27 padding keys (score 0, v = 0) join the row sum; drop_last: key 196 is masked with them -- the two mask faults."""
     q, k, v = (_cv(x, dt).float() for x in (q, k, v))
     s = q @ k.transpose(-1, -2)

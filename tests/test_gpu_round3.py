@@ -109,7 +109,7 @@ def test_fc2_leading_ktile_option_does_not_change_results(precision, mode):
 
 @pytest.mark.parametrize("B", [1, 3, 128])
 def test_fused_attention_backward_is_bitwise_the_two_kernel_form(B):
-    """attn_bwd_fused_bf16_kernel (dK/dV phase and dQ phase of a head in one persistent workgroup pass, csrc/attention.hip) runs
+    """attn_bwd_fused_bf16_kernel (dK/dV phase and dQ phase of a head in one persistent workgroup pass, csrc/attention_16.hip) runs
     the arithmetic of the two separate kernels on the same operands: dq, dk, dv must be the same bits, in both 16-bit operand
     types, at 1 / 3 / 1536 (image, head) pairs per launch (B=128 = the bench size: 6 heads per persistent workgroup).
     Reference op: Attention.forward's autograd backward, models/vision_transformer_IN21K.py:60-70."""

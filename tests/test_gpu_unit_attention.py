@@ -1,4 +1,4 @@
-"""Unit tests of the attention kernels (csrc/attention.hip, csrc/attention_v2.hip), each route of csrc/attn_route.h launched alone through
+"""Unit tests of the attention kernels (csrc/attention_16.hip, attention_exact.hip, attention_split.hip, attention_v2.hip), each route of csrc/attn_route.h launched alone through
 dyt_unit_attn_fwd / dyt_unit_attn_bwd and compared element by element with the fp64 references of tests/attn_refs.py (pinned to torch
 autograd by tests/test_attn_refs_host.py).  DESIGN.md 7v holds the derivations.
 
@@ -40,7 +40,7 @@ F16, F32, F64 = torch.float16, torch.float32, torch.float64
 NT, NH, HD, D = R.NT, R.NH, R.HD, R.D
 ERR = -1          # DYT_ERR_ARG, and what launch_attn_fwd / launch_attn_bwd return for a refused route
 SEED = 5
-GS_UNIT = 4096.0  # attention.hip launch_attn_bwd: the lift of dout in the split backward kernels when no dqkv3 is asked for
+GS_UNIT = 4096.0  # attention_split.hip launch_attn_bwd_split: the lift of dout in the split backward kernels when no dqkv3 is asked for
 WORST_A = {}      # kernel -> (worst share of the allowance, case)
 _SWITCHES = {}    # library -> (DYT_OPT_ATTN_V2, DYT_OPT_ATTN_BWD_FUSED) as _switches() last set them (the libraries' defaults: 3, 1)
 T0 = time.time()
@@ -531,6 +531,30 @@ def test_strided_out_equals_the_contiguous_call(route, mode):
     _same_bits(strided, flat, tag + "dqkv")
     if route != "AB_V2":
         _same_bits(delta2, delta, tag + "delta")
+
+
+@pytest.mark.parametrize("mode", MODES16)
+@pytest.mark.parametrize("case", ["strided out", "cls-only tail"])
+def test_fused_routes_equal_the_two_kernel_form(case, mode):
+    """The fused kernels run the two phase bodies of the two-kernel form (attention_16.hip: bwd16_dkv_phase, bwd16_dq_phase), so AB_16_FUSED
+    and AB_16_FUSED_AHEAD give AB_16_TWO's dq, dk and dv (torch.equal) in the two calls whose argument only the fused kernels' phases see
+    differently: a strided `out` (out_ld = 1536), and a cls-only dout with q_tiles = 1 against the two-kernel form's seven query tiles."""
+    L, _, dt, _ = _mode(mode)
+    B = 2
+    M = B * NT
+    cls = case == "cls-only tail"
+    c = _ref("randn", B, dt, "cls" if cls else "randn")
+    tag = "%s B=%d %s: " % (mode, B, case)
+    ops, extra = _bwd_ops16(c, dt), {}
+    if not cls:
+        img = torch.full((M, 2 * D), math.nan, dtype=dt, device=DEV)
+        img[:, :D] = ops["out"]
+        ops, extra = dict(ops, out=img), dict(out_ld=2 * D)
+    two, _ = _run_bwd16(L, "AB_16_TWO", c, dt, tag + "AB_16_TWO ", ops, q_tiles=7, **extra)
+    for route in ("AB_16_FUSED", "AB_16_FUSED_AHEAD"):
+        got, _ = _run_bwd16(L, route, c, dt, tag + route + " ", ops, q_tiles=1 if cls else 7, **extra)
+        for i, name in enumerate(("dq", "dk", "dv")):
+            assert torch.equal(got[:M, i * D:(i + 1) * D], two[:M, i * D:(i + 1) * D]), tag + "%s of %s differs from AB_16_TWO" % (name, route)
 
 
 # ==================================================================================================================================
