@@ -506,6 +506,20 @@ class UnitAttnBwdArgs(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("out_ld", "out_hi_only", "split16", "grad_parts", "q_tiles", "batch")] + \
                [("s3", _f)]
 
+
+class UnitWgradArgs(ctypes.Structure):
+    """dyt_unit_wgrad_args (include/dyt_hip.h): WgradArgs of csrc/kernels.h field for field as a plain C struct; unset pointers are NULL."""
+    _fields_ = [("X", _vp), ("Y", _vp), ("M", ctypes.c_int32), ("r", ctypes.c_int32), ("partial", _vp),
+                ("out_w", _vp), ("sc", ctypes.c_int32), ("sj", ctypes.c_int32), ("alpha", _f),
+                ("out_xsum", _vp), ("alpha_x", _f), ("out_ysum", _vp), ("alpha_y", _f),
+                ("half_products", ctypes.c_int32), ("x_scale", _f), ("y_scale", _f), ("alpha_dev", _vp)]
+
+
+class UnitTokReduceArgs(ctypes.Structure):
+    """dyt_unit_tok_reduce_args (include/dyt_hip.h): one queue_tok_reduce call -- partial [nparts][769], out[769]."""
+    _fields_ = [("partial", _vp), ("nparts", ctypes.c_int32), ("out", _vp)]
+
+
 # every symbol include/dyt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dyt_last_error": (ctypes.c_char_p, []),
@@ -582,6 +596,8 @@ SYMBOLS = {
     "dyt_unit_pad_convert": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dyt_unit_attn_fwd": (_i, [ctypes.POINTER(UnitAttnFwdArgs), _i, _vp]),
     "dyt_unit_attn_bwd": (_i, [ctypes.POINTER(UnitAttnBwdArgs), _i, _vp]),
+    "dyt_unit_wgrad": (_i, [ctypes.POINTER(UnitWgradArgs), _i, _i, _i, ctypes.POINTER(UnitTokReduceArgs), _i, _i, _vp]),
+    "dyt_unit_reduce_partials": (_i, [_vp, _i, _i, _vp, _i, _f, _vp]),
     "dyt_gemm_bf16_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_gemm_f32_raw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "dyt_wgrad_scratch_floats": (ctypes.c_int64, [_i]),
@@ -603,7 +619,8 @@ OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd",
                     "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",
                     "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert", "dyt_unit_attn_fwd", "dyt_unit_attn_bwd",
-                    "dyt_forward_taps", "dyt_backward_tokens", "dyt_unit_ln_bwd_tap"}
+                    "dyt_forward_taps", "dyt_backward_tokens", "dyt_unit_ln_bwd_tap",
+                    "dyt_unit_wgrad", "dyt_unit_reduce_partials"}
 
 _lib16 = None
 

@@ -798,3 +798,59 @@ extern "C" int dyt_unit_attn_bwd(const dyt_unit_attn_bwd_args* p, int precision,
     DYT_HIP_CHECK(hipStreamSynchronize(s));
     return DYT_OK;
 }
+
+// ---- the weight-gradient and partial-reduction kernels alone (wgrad.hip): the struct is WgradArgs of kernels.h field for field, the caller owns
+// ---- every buffer.  Argument checks, launch_wgrad / queue_tok_reduce / flush_reductions / launch_reduce_partials as backward.hip and step.hip
+// ---- call them, synchronise.  No arithmetic, no kernels here.  Test-only (tests/test_gpu_unit_wgrad.py). ----
+extern "C" int dyt_unit_wgrad(const dyt_unit_wgrad_args* prods, int n_prod, int pair, int defer, const dyt_unit_tok_reduce_args* toks, int n_tok,
+                              int precision, void* stream) {
+    { int rc = unit_precision_ok("dyt_unit_wgrad", precision); if (rc) return rc; }
+    if (!prods) { set_error("dyt_unit_wgrad: prods is NULL"); return DYT_ERR_ARG; }
+    if (n_prod < 1 || n_prod > ReduceQueue::MAX_WG) { set_error("dyt_unit_wgrad: n_prod = %d (1..%d)", n_prod, ReduceQueue::MAX_WG); return DYT_ERR_ARG; }
+    if (n_tok < 0 || n_tok > ReduceQueue::MAX_TOK) { set_error("dyt_unit_wgrad: n_tok = %d (0..%d)", n_tok, ReduceQueue::MAX_TOK); return DYT_ERR_ARG; }
+    if (n_tok > 0 && !defer) { set_error("dyt_unit_wgrad: n_tok = %d without defer (token reductions exist in the queue only)", n_tok); return DYT_ERR_ARG; }
+    if (n_tok > 0 && !toks) { set_error("dyt_unit_wgrad: toks is NULL with n_tok = %d", n_tok); return DYT_ERR_ARG; }
+    if (pair && (n_prod & 1)) { set_error("dyt_unit_wgrad: odd n_prod = %d with pair", n_prod); return DYT_ERR_ARG; }
+    for (int i = 0; i < n_prod; ++i) {
+        const dyt_unit_wgrad_args& p = prods[i];
+        if (!p.X || !p.Y || !p.partial || !p.out_w) { set_error("dyt_unit_wgrad: product %d: X / Y / partial / out_w is NULL", i); return DYT_ERR_ARG; }
+        if (p.r < 1 || p.r > RP) { set_error("dyt_unit_wgrad: product %d: r = %d (1..%d)", i, p.r, RP); return DYT_ERR_ARG; }
+        if (p.M < 1) { set_error("dyt_unit_wgrad: product %d: M = %d < 1", i, p.M); return DYT_ERR_ARG; }
+        if (p.half_products && precision != 0) { set_error("dyt_unit_wgrad: product %d: half_products exists at precision 0 only", i); return DYT_ERR_ARG; }
+        if (!(p.x_scale > 0.f) || !(p.y_scale > 0.f)) { set_error("dyt_unit_wgrad: product %d: x_scale = %g, y_scale = %g (> 0)", i, p.x_scale, p.y_scale); return DYT_ERR_ARG; }
+    }
+    for (int i = 0; i < n_tok; ++i)
+        if (!toks[i].partial || !toks[i].out || toks[i].nparts < 1) { set_error("dyt_unit_wgrad: token reduction %d: partial / out is NULL or nparts = %d < 1", i, toks[i].nparts); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ReduceQueue rq;
+    ReduceQueue* q = defer ? &rq : nullptr;
+    const int per = pair ? 2 : 1;
+    int rc = 0;
+    for (int i = 0; i < n_prod && !rc; i += per) {
+        WgradArgs w[2];
+        for (int k = 0; k < per; ++k) {
+            const dyt_unit_wgrad_args& p = prods[i + k];
+            WgradArgs& a = w[k];
+            a.X = p.X; a.Y = p.Y; a.M = p.M; a.r = p.r; a.partial = p.partial;
+            a.out_w = p.out_w; a.sc = p.sc; a.sj = p.sj; a.alpha = p.alpha;
+            a.out_xsum = p.out_xsum; a.alpha_x = p.alpha_x; a.out_ysum = p.out_ysum; a.alpha_y = p.alpha_y;
+            a.half_products = p.half_products != 0; a.x_scale = p.x_scale; a.y_scale = p.y_scale; a.alpha_dev = p.alpha_dev;
+        }
+        rc = launch_wgrad(precision, w, per, s, q);
+    }
+    for (int i = 0; i < n_tok && !rc; ++i) rc = queue_tok_reduce(rq, toks[i].partial, toks[i].nparts, toks[i].out);
+    if (!rc && defer) rc = flush_reductions(rq, s);
+    if (rc) { hipStreamSynchronize(s); return rc; }   // (what was accepted before the refusal has finished; the error text is the launcher's)
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}
+
+extern "C" int dyt_unit_reduce_partials(const float* partial, int nparts, int stride, float* out, int n, float alpha, void* stream) {
+    if (!partial || !out) { set_error("dyt_unit_reduce_partials: partial / out is NULL"); return DYT_ERR_ARG; }
+    if (nparts < 1 || n < 1 || stride < 0) { set_error("dyt_unit_reduce_partials: nparts = %d, n = %d (>= 1), stride = %d (>= 0)", nparts, n, stride); return DYT_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_reduce_partials(partial, nparts, stride, out, n, alpha, s);
+    if (rc) return rc;
+    DYT_HIP_CHECK(hipStreamSynchronize(s));
+    return DYT_OK;
+}

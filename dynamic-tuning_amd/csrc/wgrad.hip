@@ -388,6 +388,8 @@ int launch_wgrad(int precision, const WgradArgs* a, int n, hipStream_t s, Reduce
         outs.p[i] = WgOut{w.partial, w.out_w, w.sc, w.sj, w.alpha / (xs * ys), w.out_xsum, w.alpha_x / xs, w.out_ysum, w.alpha_y / ys, w.alpha_dev};
     }
     if (precision == 0 && a[0].half_products != (n == 2 ? a[1].half_products : a[0].half_products)) { set_error("launch_wgrad: mixed product forms in a pair"); return -1; }
+    // (refused before the product kernel is enqueued: a refused call writes nothing, `partial` included)
+    if (defer && (defer->n_wg + n > ReduceQueue::MAX_WG || (defer->n_wg > 0 && defer->r != r))) { set_error("reduce queue full / mixed ranks"); return -1; }
     if (precision == 0 && a[0].half_products) hipLaunchKernelGGL(wgrad_bf16_kernel<float>, dim3(D / 128, nchunks, n), dim3(256), 0, s, src, M, chunk);
     else if (precision == 0) hipLaunchKernelGGL(wgrad_f32_kernel, dim3(D / 128, nchunks, n), dim3(256), 0, s, src, M, chunk);
     else {
@@ -401,7 +403,6 @@ int launch_wgrad(int precision, const WgradArgs* a, int n, hipStream_t s, Reduce
         hipLaunchKernelGGL(wgrad_bf16_kernel<bf16>, dim3(D / 128, nchunks, n), dim3(256), extra, s, src, M, chunk);
     }
     if (defer) {
-        if (defer->n_wg + n > ReduceQueue::MAX_WG || (defer->n_wg > 0 && defer->r != r)) { set_error("reduce queue full / mixed ranks"); return -1; }
         defer->r = r;
         for (int i = 0; i < n; ++i) {
             const WgOut& o = outs.p[i];

@@ -783,6 +783,38 @@ typedef struct {
 } dyt_unit_attn_bwd_args;
 int dyt_unit_attn_bwd(const dyt_unit_attn_bwd_args* args, int precision, void* stream);
 
+/* ---- the weight-gradient and partial-reduction kernels alone (csrc/wgrad.hip), for tests/test_gpu_unit_wgrad.py.  As above: each entry checks
+ * its arguments (DYT_ERR_ARG with a text, before anything is enqueued), calls the launcher csrc/backward.hip / csrc/step.hip call, and
+ * synchronises; no arithmetic and no kernel of its own.  Added without an ABI version change, discovered by their symbols.
+ * dyt_unit_wgrad_args is WgradArgs of csrc/kernels.h field for field (bool as int32); the caller owns every buffer, `partial` (the number of
+ * floats dyt_wgrad_scratch_floats(M) returns, one buffer per product) included.  Per product, with X [M,768] and Y [M,64] of the operand type (fp32 at
+ * precision 0) and a = alpha_dev ? *alpha_dev : 1:
+ *   out_w[c * sc + j * sj] += alpha a sum_m X[m][c] Y[m][j]  (c < 768, j < r; columns j >= r of Y are read and have no effect)
+ *   out_xsum[c] += alpha_x a sum_m X[m][c]   (when given)        out_ysum[j] += alpha_y a sum_m Y[m][j], j < r   (when given)
+ * half_products (precision 0 only): X x_scale and Y y_scale (powers of two) are rounded to the library's 16-bit type as they are loaded,
+ * the products run on the 16-bit matrix cores and alpha / (x_scale y_scale), alpha_x / x_scale, alpha_y / y_scale undo the scales.
+ * pair = 1: consecutive products go two by two through one launch_wgrad(P, w, 2, ...) (same M and r, different `partial`), else one by one.
+ * defer = 1: every reduction is queued into ONE ReduceQueue together with the n_tok token reductions (queue_tok_reduce:
+ * out[i] += sum_p partial[p * 769 + i], i < 769, p < nparts) and flush_reductions runs once at the end (wgrad_reduce_batch_kernel,
+ * reduce_partials_batch_kernel); defer = 0: wgrad_reduce_kernel behind each launch, n_tok must be 0.
+ * DYT_ERR_ARG, nothing launched: prods NULL; n_prod outside 1..32 (ReduceQueue::MAX_WG); n_tok outside 0..16 (MAX_TOK) or non-zero without
+ * defer or with toks NULL; an odd n_prod with pair; a precision outside {0, 1}; per product NULL X / Y / partial / out_w, r outside 1..64,
+ * M < 1, half_products at precision 1, x_scale or y_scale not positive; per token reduction NULL partial / out or nparts < 1.  The
+ * launcher's own refusals (a pair with different M or r or one `partial`; mixed product forms in a pair; mixed ranks in a queue) come back
+ * as its error, before the refused product's kernel is enqueued; products accepted before it have run, their reductions have not. */
+typedef struct {
+    const void* X; const void* Y; int32_t M, r; float* partial;
+    float* out_w; int32_t sc, sj; float alpha;
+    float* out_xsum; float alpha_x; float* out_ysum; float alpha_y;
+    int32_t half_products; float x_scale, y_scale; const float* alpha_dev;
+} dyt_unit_wgrad_args;
+typedef struct { const float* partial; int32_t nparts; float* out; } dyt_unit_tok_reduce_args;
+int dyt_unit_wgrad(const dyt_unit_wgrad_args* prods, int n_prod, int pair, int defer, const dyt_unit_tok_reduce_args* toks, int n_tok,
+                   int precision, void* stream);
+/* reduce_partials_kernel (launch_reduce_partials): out[i] += alpha sum_p partial[p * stride + i], i < n, p < nparts.
+ * DYT_ERR_ARG: NULL partial / out, nparts < 1, n < 1, stride < 0. */
+int dyt_unit_reduce_partials(const float* partial, int nparts, int stride, float* out, int n, float alpha, void* stream);
+
 /* One nn.Linear (c = a w^T + bias; a [M,K], w [N,K], bias [N] or NULL, c [M,N], fp32 device pointers) through the split forms of the
  * fp32 mode: form 3 = every product as three IEEE-half products (hi*hi + hi*lo + lo*hi), form 8 = hi*hi on the f16 matrix cores plus
  * the two correction products on the fp8 (e4m3) matrix cores ("fp16f8").  K % 128 == 0, N % 128 == 0.  Unit-test entry: allocates

@@ -40,8 +40,9 @@ test_tok_bwd_16bit_adapter_dgrad_and_stream[fp16]; `/ a.tau` skipped, or rv read
 resp. with dA2 (26 cases each); dmask_next from the gs-scaled row in ln_bwd_kernel -- test_ln_bwd[3 / 4 / 5 / 197-fp16].
 
 Not reachable from here: the kernels' behaviour under a concurrently running stream (the reason for their full vmcnt drains, DESIGN.md
-7b) -- the entries launch them alone; reduce_partials_batch_kernel with more than one queued pair (blockIdx.y > 0) and the adapter
-weight-gradient half of flush_reductions; M beyond 591 tokens (the index arithmetic is size_t throughout)."""
+7b) -- the entries launch them alone; M beyond 591 tokens (the index arithmetic is size_t throughout).  (reduce_partials_batch_kernel with
+more than one queued pair, blockIdx.y > 0, and the adapter weight-gradient half of flush_reductions are reached by
+tests/test_gpu_unit_wgrad.py.)"""
 import ctypes
 import math
 import os
