@@ -559,6 +559,7 @@ SYMBOLS = {
     "dyt_adamw": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _f, _f, _f, _f, _f, _vp]),
     "dyt_adamw_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _vp]),
     "dyt_adamw_segments": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp]),
+    "dyt_ema_update": (_i, [_vp, _vp, _i64, _f, _f, _vp]),
     "dyt_step_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _u64, _f, _f, _f, _f, _vp, _vp, _vp, _vp,
                               _vp, _vp]),
     "dyt_seed": (_i, [_vp, _u64, _vp]),
@@ -620,7 +621,7 @@ OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u
                     "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",
                     "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert", "dyt_unit_attn_fwd", "dyt_unit_attn_bwd",
                     "dyt_forward_taps", "dyt_backward_tokens", "dyt_unit_ln_bwd_tap",
-                    "dyt_unit_wgrad", "dyt_unit_reduce_partials"}
+                    "dyt_unit_wgrad", "dyt_unit_reduce_partials", "dyt_ema_update"}
 
 _lib16 = None
 

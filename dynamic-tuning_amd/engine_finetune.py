@@ -22,6 +22,7 @@ from util.erasing import DeviceRandomErasing
 from util.crop import (DeviceClipRandomResizedCrop, DeviceClipScaleJitterCrop, DeviceClipUniformCrop, DeviceRandomResizedCrop,
                        DeviceResizeCenterCrop, _DeviceClipCrop, full_clip_sizes, full_sizes, probe_clip_draw, probe_draw)
 from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
+from util.model_ema import DeviceModelEma
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
 
@@ -738,6 +739,19 @@ def _device_erasing(args, cube_default=False):
     return cached
 
 
+def _model_ema(args, model):
+    """``args.model_ema``: None / absent (no averaging: the loop launches what it always did), or the util.model_ema.DeviceModelEma of this
+    model; anything else is refused by its class name (a host-side ModelEmaV2 would deep-copy a module that owns a library context)."""
+    ema = getattr(args, "model_ema", None) if args is not None else None
+    if ema is None:
+        return None
+    if not isinstance(ema, DeviceModelEma):
+        raise DyTError("args.model_ema must be a util.model_ema.DeviceModelEma or None (got %s)" % type(ema).__name__)
+    if ema.model is not getattr(model, "module", model):
+        raise DyTError("args.model_ema averages another model than the one this loop trains")
+    return ema
+
+
 def _device_crop(args, name, kind, model, video=False):
     """``args.device_crop`` / ``args.device_eval_crop``, or None.  Images: a util.crop.DeviceRandomResizedCrop / DeviceResizeCenterCrop
     (``kind``); the cropped batch is bytes.  Video (``video``): a DeviceClipScaleJitterCrop or DeviceClipRandomResizedCrop /
@@ -838,7 +852,11 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     util.crop.DeviceClipScaleJitterCrop or DeviceClipRandomResizedCrop: the loader yields ``((clips uint8 [B, T, Hs, Ws, 3], sizes), labels)``
     (util.crop.pad_collate_clips) and the loop writes the normalised, resized, cropped and mirrored fp32 clips [B, 3, T, 224, 224] on the
     device, in front of the step and outside its captured graph.  Erasing and mixing then act on that float clip -- the erasing AFTER the
-    mirror, where the reference's dataset erases before it (the shipped video configs use no erasing)."""
+    mirror, where the reference's dataset erases before it (the shipped video configs use no erasing).
+    ``args.model_ema`` (a util.model_ema.DeviceModelEma built on this model): ``update()`` after every optimizer update -- once per
+    ``accum_iter`` micro-batches, on the compute stream behind the AdamW launch, outside the captured graph -- whether or not the overflow
+    guard skipped that update."""
+    ema = _model_ema(args, model)
     optimizer = as_fused(optimizer, model)
     eraser = _device_erasing(args, cube_default=_video)
     cropper = _device_crop(args, "device_crop", DeviceRandomResizedCrop, getattr(model, "module", model), video=_video)
@@ -881,6 +899,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         train_step(model, samples, targets, optimizer, criterion, losses_out=step_losses, seed=step_seed(epoch, it),
                    gumbel=gumbel, keep_mask=keep_mask, accumulate=(it % accum_iter != 0), update=((it + 1) % accum_iter == 0),
                    accum_iter=accum_iter, max_norm=max_norm or 0.0, graph=use_graph, mix=mix, erase=erase)
+        if ema is not None and (it + 1) % accum_iter == 0:   # behind optimizer.step(), like model_ema.update(model) behind loss_scaler(...)
+            ema.update()
         acc += step_losses
         pending += 1
         if (it + 1) % print_freq == 0 or it + 1 == nsteps:

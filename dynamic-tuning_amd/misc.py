@@ -12,9 +12,11 @@ engine_finetune.py touch in it (reference misc.py:24-363), so that this file can
   guarded optimizer step on the generic autograd route;
 * checkpoints: ``save_model`` / ``load_model`` (:296-352), same file format
   ``{'model', 'optimizer', 'epoch', 'scaler', 'args'}`` with the reference's parameter names; the optimizer entry is in
-  ``torch.optim.AdamW.state_dict()`` layout whichever optimizer object the driver holds.
+  ``torch.optim.AdamW.state_dict()`` layout whichever optimizer object the driver holds.  With ``args.model_ema`` (a
+  util.model_ema.DeviceModelEma) the file gains ``'model_ema'`` (the averaged trainable tensors) and ``'model_ema_updates'``.
 """
 import builtins
+import copy
 import datetime
 import math
 import os
@@ -295,6 +297,15 @@ def _scaler_entry(optimizer, loss_scaler):
     return fused.scaler_state() if hasattr(fused, "scaler_state") else {}
 
 
+def _args_without(args, name):
+    slim = copy.copy(args)
+    try:
+        delattr(slim, name)
+    except AttributeError:
+        pass
+    return slim
+
+
 def save_model(args, epoch, model, model_without_ddp, optimizer, loss_scaler=None, save_force=False):
     """Reference :296-331: ``checkpoint-<epoch>.pth`` on rank 0 every ``save_freq`` epochs, at the last epoch or when forced;
     ``auto_remove`` deletes older ones."""
@@ -305,13 +316,19 @@ def save_model(args, epoch, model, model_without_ddp, optimizer, loss_scaler=Non
     fused = getattr(optimizer, "_dyt_fused", None)
     if fused is not None:
         fused.publish_torch_state()   # the driver's torch.optim.AdamW reports the fused optimizer's moments and step count
-    save_on_master({
+    checkpoint = {
         'model': {k: v.detach().cpu() for k, v in model_without_ddp.state_dict().items()},
         'optimizer': _to_cpu(optimizer.state_dict()) if optimizer is not None else None,
         'epoch': epoch,
         'scaler': _scaler_entry(optimizer, loss_scaler),
         'args': args,
-    }, out / ('checkpoint-%s.pth' % epoch))
+    }
+    ema = getattr(args, "model_ema", None)
+    if ema is not None:   # the averaged trainable tensors alone (~5 MB): the frozen ones are the model's
+        checkpoint['model_ema'] = _to_cpu(ema.state_dict())
+        checkpoint['model_ema_updates'] = int(ema.updates)
+        checkpoint['args'] = _args_without(args, "model_ema")   # (the object holds device buffers and the model: not part of the record)
+    save_on_master(checkpoint, out / ('checkpoint-%s.pth' % epoch))
     if getattr(args, "auto_remove", False):
         for name in os.listdir(args.output_dir):
             if not (name.startswith('checkpoint-') and name.endswith('.pth')):
@@ -335,6 +352,10 @@ def load_model(args, model_without_ddp, optimizer, loss_scaler=None):
     weights = checkpoint.get('model', checkpoint.get('module', checkpoint))
     model_without_ddp.load_state_dict(weights)
     print("Resume checkpoint %s" % args.resume)
+    ema = getattr(args, "model_ema", None)
+    if ema is not None and 'model_ema' in checkpoint:   # (a checkpoint without the keys leaves the shadow at its construction snapshot)
+        ema.load_state_dict(checkpoint['model_ema'])
+        ema.updates = int(checkpoint.get('model_ema_updates', 0))
     if 'optimizer' in checkpoint and 'epoch' in checkpoint and not getattr(args, 'eval', False):
         if optimizer is not None and checkpoint['optimizer'] is not None:
             optimizer.load_state_dict(checkpoint['optimizer'])

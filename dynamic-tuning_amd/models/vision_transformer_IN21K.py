@@ -411,6 +411,21 @@ class VisionTransformer(nn.Module):
             raise DyTError("%s with grad enabled: the model was built with inference_only and saves nothing for a backward pass; call it "
                            "under torch.no_grad() (or requires_grad_(False)), or build it without inference_only" % what)
 
+    def _eval_trainable(self, what, trainable, eng):
+        """``trainable=`` of ``_forward`` / ``_forward_features``: another flat buffer the pass reads the trainable tensors from (the averaged
+        model of util.model_ema.DeviceModelEma).  Eval forwards alone: nothing could carry a gradient to that buffer."""
+        if trainable is None:
+            return None
+        if self.training or torch.is_grad_enabled():
+            raise DyTError("%s(trainable=...): an eval forward on another trainable buffer -- call it in eval() mode under torch.no_grad() "
+                           "(got %s mode, grad %s)" % (what, "train()" if self.training else "eval()", "enabled" if torch.is_grad_enabled() else "off"))
+        if callable(trainable):   # engine -> buffer: asked once this pass's engine exists (a larger batch may just have re-created it)
+            trainable = trainable(eng)
+        if not (torch.is_tensor(trainable) and trainable.dtype == torch.float32 and trainable.device == eng.flat.device and
+                trainable.is_contiguous() and trainable.numel() == eng.n_train):
+            raise DyTError("%s(trainable=...): a contiguous fp32 tensor of %d elements on %s" % (what, eng.n_train, eng.flat.device))
+        return trainable
+
     # ---- reference API ------------------------------------------------------------------------
     def forward(self, x, complete_model=False, gumbel=None, keep_mask=None):
         """x [B,3,224,224] -> (logits [B,C], {"token_select": [B,12,196,1], "token_logits": [B,12,196,1]}).
@@ -419,11 +434,17 @@ class VisionTransformer(nn.Module):
         ``gumbel=(g1, g2)`` ([depth,B,196] each) and ``keep_mask`` ([depth,B*197,r] uint8) inject the
         training-mode random draws (parity tests); by default they come from the on-device Philox
         stream seeded from torch's seed and a per-model call counter."""
+        return self._forward(x, complete_model, gumbel, keep_mask)
+
+    def _forward(self, x, complete_model=False, gumbel=None, keep_mask=None, trainable=None):
+        """``forward``.  ``trainable``: a flat fp32 buffer in the engine's trainable layout (or a callable engine -> buffer) that this pass
+        reads instead of the model's own parameters -- eval mode, no grad; the model's parameters are not written (util.model_ema)."""
         if not x.is_cuda:
             raise DyTError("DyT VisionTransformer runs on a HIP device only (input is on %s); there is no CPU path" % x.device)
         self._refuse_training("forward")
         x = self.prepare_input(x)
         eng = self.engine(x.shape[0], x.device)
+        trainable = self._eval_trainable("forward", trainable, eng)
         # FLOP-probe variant (reference Block.forward_count_flops :167-185, set through
         # `model.apply(lambda m: setattr(m, "count_flops", True))` / `token_select_num` as block_flops_dict.get_block_flops
         # :33-55 does): every block runs its MLP on the first `token_select_num` tokens
@@ -448,7 +469,7 @@ class VisionTransformer(nn.Module):
         else:
             logits, ts, tl = eng.forward(x, slot=1 if complete_model else 0, training=self.training,
                                          complete_model=bool(complete_model), save=False, gate_always=True, g1=g1, g2=g2,
-                                         keep_mask=keep_mask, seed=seed)
+                                         keep_mask=keep_mask, seed=seed, trainable=trainable)
         return logits, dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))
 
     def _final_norm(self, tok):
@@ -476,6 +497,10 @@ class VisionTransformer(nn.Module):
         get none, the final ``norm`` is frozen.  The caller owns head, loss and optimizer.  Under ``torch.no_grad()``, in inference-only
         models, and in eval() mode without ``out_indices`` (the call as it was before it became differentiable: the same bits) it is the
         forward alone; an eval-mode model is differentiated by naming ``out_indices``."""
+        return self._forward_features(x, complete_model, gumbel, keep_mask, out_indices)
+
+    def _forward_features(self, x, complete_model=False, gumbel=None, keep_mask=None, out_indices=None, trainable=None):
+        """``forward_features``.  ``trainable``: as in ``_forward``."""
         from _lib import check_out_indices
         if not x.is_cuda:
             raise DyTError("DyT VisionTransformer runs on a HIP device only (input is on %s); there is no CPU path" % x.device)
@@ -486,6 +511,7 @@ class VisionTransformer(nn.Module):
         self._refuse_training("forward_features", grad_check=False)
         x = self.prepare_input(x)
         eng = self.engine(x.shape[0], x.device)
+        trainable = self._eval_trainable("forward_features", trainable, eng)
         g1 = g2 = None
         if gumbel is not None:
             g1, g2 = (t.to(x.device, torch.float32).contiguous() for t in gumbel)
@@ -507,7 +533,7 @@ class VisionTransformer(nn.Module):
         else:
             res = eng.forward_features_tokens(x, training=self.training, complete_model=bool(complete_model),
                                               masked_dense=(self.training and self.train_mode == "masked"), g1=g1, g2=g2, keep_mask=keep_mask,
-                                              seed=seed, taps=out_indices)
+                                              seed=seed, taps=out_indices, trainable=trainable)
             tok, taps, ts, tl = res if out_indices is not None else (res[0], (), res[1], res[2])
             out = tok if self.use_fc_norm else self._final_norm(tok)
         aux = dict(token_select=ts.unsqueeze(-1), token_logits=tl.unsqueeze(-1))

@@ -225,15 +225,17 @@ class DyTEngine:
         return out, ts, tl
 
     def forward_features_tokens(self, images, training=False, complete_model=False, masked_dense=False, g1=None, g2=None, keep_mask=None, seed=0,
-                                save=False, taps=None, slot=0):
+                                save=False, taps=None, slot=0, trainable=None):
         """Images in, the block stack's output tokens out (DYT_F_TOKENS_OUT without DYT_F_TOKENS_IN): what the reference's forward_features
         holds right before its final norm (vision_transformer_IN21K.py:343-368).  Returns (tokens [B,197,768],
         token_select [B,depth,196], token_logits [B,depth,196]).
 
         ``taps``: block indices in [0, depth) -- the residual stream behind each of those blocks, un-normalised, is returned as well
         (dyt_forward_taps): ``(tokens, taps, token_select, token_logits)`` with ``taps`` a tuple of [B,197,768] tensors in the order given.
-        ``save=True`` keeps the pass in ``slot`` for ``backward_tokens``."""
+        ``save=True`` keeps the pass in ``slot`` for ``backward_tokens``.  ``trainable``: another flat buffer than ``self.flat`` to read the
+        trainable tensors from, as in ``forward`` (the averaged model of util.model_ema)."""
         B = images.shape[0]
+        tr = self.flat if trainable is None else trainable
         flags = ((F_TRAINING if training else 0) | (F_COMPLETE if complete_model else 0) | (F_MASKED_DENSE if masked_dense else 0) |
                  (F_SAVE if save else 0) | F_GATE_ALWAYS | F_TOKENS_OUT | self._image_flags(images))
         if training:
@@ -243,7 +245,7 @@ class DyTEngine:
         tl = torch.zeros(B, self.depth, NP, device=self.device, dtype=torch.float32)
         if taps is None and not save:
             with torch.cuda.device(self.device):
-                self._ck(self.L.dyt_forward(self.h, slot, ptr(images), B, flags, ptr(self.flat), ptr(g1), ptr(g2), ptr(keep_mask),
+                self._ck(self.L.dyt_forward(self.h, slot, ptr(images), B, flags, ptr(tr), ptr(g1), ptr(g2), ptr(keep_mask),
                                          ctypes.c_uint64(seed & (2 ** 64 - 1)), ptr(out), ptr(ts), ptr(tl), stream_ptr()))
             return out, ts, tl
         if not hasattr(self.L, "dyt_forward_taps"):
@@ -254,7 +256,7 @@ class DyTEngine:
         if save:
             self.generation[slot] += 1
         with torch.cuda.device(self.device):
-            self._ck(self.L.dyt_forward_taps(self.h, slot, ptr(images), B, flags, ptr(self.flat), ptr(g1), ptr(g2), ptr(keep_mask),
+            self._ck(self.L.dyt_forward_taps(self.h, slot, ptr(images), B, flags, ptr(tr), ptr(g1), ptr(g2), ptr(keep_mask),
                                              ctypes.c_uint64(seed & (2 ** 64 - 1)), ptr(out), ptr_array(bufs, self.depth), ptr(ts), ptr(tl),
                                              stream_ptr()))
         if taps is None:
@@ -399,6 +401,21 @@ class DyTEngine:
             self._ck(self.L.dyt_adamw_segments(ptr(self.flat), ptr(self.grad), ptr(exp_avg), ptr(exp_avg_sq), self.n_train, ptr(state),
                                             int(step), ctypes.cast(arr, ctypes.c_void_p), len(table), beta1, beta2, eps, grad_scale,
                                             stream_ptr()))
+
+    def ema_update(self, shadow, decay):
+        """dyt_ema_update on torch's current stream: ``shadow = decay * shadow + (1. - decay) * self.flat`` in place, as torch evaluates
+        timm's ModelEmaV2 update on fp32 tensors (three roundings).  ``shadow``: a flat fp32 buffer in this engine's trainable layout
+        (util.model_ema.DeviceModelEma owns it).  1. - decay is formed in double here; both scalars are rounded to float once."""
+        self._refuse_inference("ema_update")
+        if not hasattr(self.L, "dyt_ema_update"):
+            raise DyTError("this libdyt_hip has no dyt_ema_update (model EMA): rebuild it")
+        if not (torch.is_tensor(shadow) and shadow.dtype == torch.float32 and shadow.device == self.flat.device and shadow.is_contiguous()):
+            raise DyTError("ema_update: the shadow is a contiguous fp32 tensor on %s" % (self.flat.device,))
+        if shadow.numel() != self.n_train:
+            raise DyTError("ema_update: the shadow holds %d elements, the engine trains %d" % (shadow.numel(), self.n_train))
+        decay = float(decay)
+        with torch.cuda.device(self.device):
+            self._ck(self.L.dyt_ema_update(ptr(shadow), ptr(self.flat), self.n_train, decay, 1. - decay, stream_ptr()))
 
     def clip_grad_norm(self, max_norm, pre_scale=1.0, norm_out=None):
         """torch.nn.utils.clip_grad_norm_ on the flat gradient (misc.py:262-266); pre_scale = the factor AdamW applies."""

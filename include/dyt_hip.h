@@ -563,6 +563,17 @@ int dyt_adamw_segments(float* param, const float* grad, float* exp_avg, float* e
                        int32_t* state, int step, const dyt_adamw_segment* segments, int num_segments,
                        float beta1, float beta2, float eps, float grad_scale, void* stream);
 
+/* Model EMA (timm's ModelEmaV2) over a flat fp32 buffer, in place and context-free:
+ *   ema[i] = fl( fl(decay * ema[i]) + fl(one_minus_decay * param[i]) )
+ * -- `ema_v.copy_(decay * ema_v + (1. - decay) * model_v)` as torch evaluates it on fp32 tensors: three fp32 roundings, no fused
+ * multiply-add, denormals kept.  The caller forms 1. - decay in double and rounds both scalars to float once.  One launch on `stream`,
+ * no atomics, no host sync; 16-byte accesses where both pointers allow them, scalar accesses for unaligned slices and the tail, the
+ * same bits either way.  numel == 0 is a successful no-op.  DYT_ERR_ARG (with an error text, before anything is enqueued): a null
+ * pointer with numel > 0, numel < 0, a pointer that is not 4-byte aligned, decay or one_minus_decay non-finite or outside [0, 1].
+ * The AdamW entries above are not involved: the update is a launch of its own behind them.
+ * Added without an ABI version change (the version stays 5): a caller discovers this entry by its symbol, like dyt_adamw_segments. */
+int dyt_ema_update(float* ema, const float* param, int64_t numel, float decay, float one_minus_decay, void* stream);
+
 /* One whole fine-tune step body (engine_finetune.py:47-79 without the host syncs): student +
  * teacher forward, loss, one backward over both passes into grad_flat (zeroed first).  The caller
  * all-reduces grad_flat (DDP, main_image.py:280-282) and then calls dyt_adamw. */
