@@ -419,6 +419,93 @@ def resample_clip_coeffs(table, row, src_h, src_w):
     return out
 
 
+RANDAUG_HEADER_WORDS, RANDAUG_ROW_WORDS, RANDAUG_HIST_WORDS, RANDAUG_TABLE_WORDS, RANDAUG_MAX_LAYERS = 16, 20, 4 * 256, 3 * 256 + 1, 8   # csrc/randaug.h
+
+
+def _randaug_args(L, pixels, table, layers, who="randaug"):
+    import torch
+    if not hasattr(L, "dyt_randaug_u8"):
+        raise DyTError("this libdyt_hip has no dyt_randaug_u8 (device RandAugment): rebuild it")
+    if not (torch.is_tensor(pixels) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() in (4, 5) and pixels.shape[-1] == 3):
+        raise DyTError("%s takes a uint8 device batch of clips [B, T, Hs, Ws, 3] or images [B, Hs, Ws, 3], channels last (got %s %s)" % (
+            who, getattr(pixels, "dtype", type(pixels)), tuple(getattr(pixels, "shape", ()))))
+    units, frames = int(pixels.shape[0]), (int(pixels.shape[1]) if pixels.dim() == 5 else 1)
+    hs, ws = int(pixels.shape[-3]), int(pixels.shape[-2])
+    if units < 1 or frames < 1 or hs < 1 or ws < 1 or hs > RESAMPLE_MAX_SIDE or ws > RESAMPLE_MAX_SIDE or units * frames > 65535:
+        raise DyTError("%s: a batch of %d units of %d frames of %d x %d (at least one, sides 1 to %d, units x frames at most 65535)" % (
+            who, units, frames, hs, ws, RESAMPLE_MAX_SIDE))
+    layers = int(layers)
+    if not (1 <= layers <= RANDAUG_MAX_LAYERS):
+        raise DyTError("%s: 1 to %d layers (got %d)" % (who, RANDAUG_MAX_LAYERS, layers))
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and
+            table.numel() >= RANDAUG_HEADER_WORDS + RANDAUG_ROW_WORDS * units * layers):
+        raise DyTError("%s table: a contiguous int32 device tensor of 16 + 20 x %d x %d words at least (util.randaug.AugDraw.words(capacity))" % (
+            who, units, layers))
+    return units, frames, hs, ws, layers, (int(table.numel()) - RANDAUG_HEADER_WORDS) // (RANDAUG_ROW_WORDS * layers)
+
+
+def randaug_u8(pixels, table, draw=None, out=None, work=None, stats=None, layers=None, launch_mask=None):
+    """dyt_randaug_u8: a uint8 device batch of clips [B, T, Hs, Ws, 3] or images [B, Hs, Ws, 3] (channels last, padded) augmented as the
+    rows of the device table ``table`` (int32 words: csrc/randaug.h, util.randaug.AugDraw.words()) say -> new bytes of the same shape, on
+    torch's current stream; the batch itself is not written.  ``draw`` (the AugDraw behind the table): checked against the batch's shape
+    on the host first -- an invalid row is refused here; the device would write that unit as zeros -- and the source of ``layers`` and the
+    launch mask; without it ``layers`` is needed and every kernel of every layer is launched.  ``out`` / ``work`` (the batch's shape) and
+    ``stats`` (int32, 1024 words per frame): buffers to use."""
+    import torch
+    L = lib()
+    if draw is not None:
+        layers = draw.layers
+        launch_mask = draw.launch_mask()
+    if layers is None:
+        raise DyTError("randaug: without a draw the number of layers must be given")
+    units, frames, hs, ws, layers, capacity = _randaug_args(L, pixels, table, layers)
+    if draw is not None:
+        if draw.units != units:
+            raise DyTError("randaug: the draw holds %d units, the batch %d" % (draw.units, units))
+        try:
+            draw.check(hs, ws)
+        except ValueError as e:
+            raise DyTError(str(e))
+    pixels = pixels.contiguous()
+    bufs = []
+    for name, b in (("out", out), ("work", work)):
+        if b is None:
+            b = torch.empty_like(pixels)
+        elif not (b.is_cuda and b.dtype == torch.uint8 and b.is_contiguous() and tuple(b.shape) == tuple(pixels.shape)):
+            raise DyTError("randaug: %s is a contiguous uint8 device tensor of the batch's shape %s" % (name, tuple(pixels.shape)))
+        bufs.append(b)
+    out, work = bufs
+    if stats is None:
+        stats = torch.empty(units * frames * RANDAUG_HIST_WORDS, device=pixels.device, dtype=torch.int32)
+    elif not (stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= units * frames * RANDAUG_HIST_WORDS):
+        raise DyTError("randaug: stats is a contiguous int32 device tensor of %d x 1024 words at least" % (units * frames))
+    mask = None
+    if launch_mask is not None:
+        if len(launch_mask) != layers:
+            raise DyTError("randaug: the launch mask has %d words for %d layers" % (len(launch_mask), layers))
+        mask = (ctypes.c_uint32 * layers)(*[int(m) for m in launch_mask])
+    with torch.cuda.device(pixels.device):
+        check(L.dyt_randaug_u8(ptr(pixels), units, frames, hs, ws, ptr(out), ptr(work), ptr(stats), ptr(table), capacity, layers, mask, stream_ptr()), L)
+    return out
+
+
+def randaug_table(pixels, table, layers, unit, frame, layer):
+    """dyt_randaug_table: the 3 x 256 table and the Contrast constant the kernels use for (unit, frame, layer) when ``pixels`` is that
+    layer's input -> int32 [769] on the device."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_randaug_table"):
+        raise DyTError("this libdyt_hip has no dyt_randaug_table (device RandAugment): rebuild it")
+    units, frames, hs, ws, layers, capacity = _randaug_args(L, pixels, table, layers, who="randaug table")
+    pixels = pixels.contiguous()
+    stats = torch.empty(units * frames * RANDAUG_HIST_WORDS, device=pixels.device, dtype=torch.int32)
+    out = torch.zeros(RANDAUG_TABLE_WORDS, device=pixels.device, dtype=torch.int32)
+    with torch.cuda.device(pixels.device):
+        check(L.dyt_randaug_table(ptr(pixels), units, frames, hs, ws, ptr(stats), ptr(table), capacity, layers, int(unit), int(frame), int(layer),
+                                  ptr(out), stream_ptr()), L)
+    return out
+
+
 # csrc/eval_stats.h / DYT_EVAL_* of include/dyt_hip.h: the int64 `counts` state of the streaming evaluation
 EVAL_HEAD_WORDS, EVAL_ROWS, EVAL_IGNORED, EVAL_NAN_ROWS, EVAL_MASK_ROWS = 8, 0, 1, 2, 3
 EVAL_RANK_BINS, EVAL_OFF_RANK, EVAL_OFF_KEEP = 16, 8, 24
@@ -546,6 +633,8 @@ SYMBOLS = {
     "dyt_resample_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dyt_resample_clip_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp]),
     "dyt_resample_clip_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "dyt_randaug_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_uint32), _vp]),
+    "dyt_randaug_table": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "dyt_eval_rows": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dyt_eval_keep": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dyt_set_frozen": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -616,7 +705,7 @@ SYMBOLS = {
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
                     "dyt_set_erase", "dyt_erase_images", "dyt_resample_u8", "dyt_resample_scratch_bytes", "dyt_resample_coeffs",
-                    "dyt_resample_clip_f32", "dyt_resample_clip_coeffs",
+                    "dyt_resample_clip_f32", "dyt_resample_clip_coeffs", "dyt_randaug_u8", "dyt_randaug_table",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd",
                     "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",
                     "dyt_unit_ln_fold_w", "dyt_unit_embed", "dyt_unit_pad_convert", "dyt_unit_attn_fwd", "dyt_unit_attn_bwd",

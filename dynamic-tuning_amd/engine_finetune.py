@@ -23,6 +23,7 @@ from util.crop import (DeviceClipRandomResizedCrop, DeviceClipScaleJitterCrop, D
                        DeviceResizeCenterCrop, _DeviceClipCrop, full_clip_sizes, full_sizes, probe_clip_draw, probe_draw)
 from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
 from util.model_ema import DeviceModelEma
+from util.randaug import DeviceRandAugment
 
 LOSS_KEYS = ("loss", "base_loss", "token_loss", "teacher_loss", "distillation_loss")
 
@@ -835,6 +836,54 @@ def _resample_clip_batch(model, cropper, samples, probe=False):
     return out.unflatten(0, (batch, tviews * cropper.views)) if evaluation else out
 
 
+def _device_randaug(args):
+    """``args.device_randaug``: None / absent (no augmentation: the loop launches and allocates what it always did), or a
+    util.randaug.DeviceRandAugment."""
+    augmenter = getattr(args, "device_randaug", None) if args is not None else None
+    if augmenter is None:
+        return None
+    if not isinstance(augmenter, DeviceRandAugment):
+        raise DyTError("args.device_randaug must be a util.randaug.DeviceRandAugment or None (got %s)" % type(augmenter).__name__)
+    return augmenter
+
+
+def _randaug_clip_batch(model, augmenter, samples, cropped):
+    """The video loop's RandAugment, in front of the clip crop (the reference's order: RandAugment -> normalise -> crop): a source batch
+    ``(clips uint8 [B, T, Hs, Ws, 3], sizes)`` or a bare uint8 tensor that every clip fills -> the same batch with augmented bytes, on the
+    current stream (DyTEngine.randaug).  Without ``args.device_crop`` (``cropped`` false) only byte clips that are already
+    [B, T, 224, 224, 3] are taken: whatever else the loader yields has been cropped and normalised on the host, behind the point where
+    the reference augments."""
+    clips, sizes = (samples[0], samples[1]) if isinstance(samples, (tuple, list)) else (samples, None)
+    ok = torch.is_tensor(clips) and clips.dtype == torch.uint8 and clips.dim() == 5 and clips.shape[-1] == 3
+    if not ok or (not cropped and tuple(clips.shape[2:4]) != (224, 224)):
+        raise DyTError("args.device_randaug: the video loop augments source byte clips [B, T, Hs, Ws, 3] in front of args.device_crop, or byte "
+                       "clips that are already [B, T, 224, 224, 3] (got %s %s%s)" % (
+                           getattr(clips, "dtype", type(clips)), tuple(getattr(clips, "shape", ())), "" if cropped else ", no args.device_crop"))
+    if getattr(model, "_frames", 1) == 1:
+        raise DyTError("args.device_randaug: the model is an image model (clips need video_models.video_vision_transformer_IN21K)")
+    frames = int(clips.shape[1])
+    if frames < 2:
+        raise DyTError("the video model needs t >= 2 frames per clip; use models.vision_transformer_IN21K for images")
+    if model._frames is not None and frames != model._frames and model._engine is not None:
+        model._engine = None   # frames per clip changed: the library context is rebuilt (as fold_input does)
+    model._frames = frames
+    given = full_clip_sizes(clips) if sizes is None else sizes
+    draw = augmenter.draw_for(given)
+    eng = model.engine(draw.units * frames, clips.device)
+    out = eng.randaug(clips, given, draw)
+    return out if sizes is None else (out, sizes)
+
+
+def _randaug_image_batch(model, augmenter, samples):
+    """The image loop's RandAugment, behind the crop and the flip (timm's order): the 224 x 224 channels-last byte batch -> augmented bytes."""
+    if not (torch.is_tensor(samples) and samples.dtype == torch.uint8 and samples.dim() == 4 and tuple(samples.shape[1:]) == (224, 224, 3)):
+        raise DyTError("args.device_randaug: the image loop augments a channels-last byte batch uint8 [B, 224, 224, 3] (float batches and "
+                       "NCHW bytes are not implemented; got %s %s)" % (getattr(samples, "dtype", type(samples)), tuple(getattr(samples, "shape", ()))))
+    sizes = full_sizes(samples)
+    eng = model.engine(samples.shape[0], samples.device)
+    return eng.randaug(samples, sizes, augmenter.draw_for(sizes))
+
+
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler=None, max_norm=0,
                     mixup_fn=None, log_writer=None, args=None, logger=None, _video=False):
     """Reference engine_finetune.py:16-106.  ``optimizer`` is the ``torch.optim.AdamW`` the drivers build (main_image.py:285;
@@ -853,6 +902,11 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     (util.crop.pad_collate_clips) and the loop writes the normalised, resized, cropped and mirrored fp32 clips [B, 3, T, 224, 224] on the
     device, in front of the step and outside its captured graph.  Erasing and mixing then act on that float clip -- the erasing AFTER the
     mirror, where the reference's dataset erases before it (the shipped video configs use no erasing).
+    ``args.device_randaug`` (a util.randaug.DeviceRandAugment; absent: not one launch or allocation changes): RandAugment on the device, in
+    front of the step and outside its captured graph.  The video loop augments the source byte clips in front of ``args.device_crop`` (the
+    reference's order: RandAugment -> normalise -> crop; without ``device_crop`` only byte clips that are already [B, T, 224, 224, 3]);
+    the image loop augments the 224 x 224 channels-last byte batch behind ``args.device_crop`` when there is one (timm's order: crop ->
+    flip -> RandAugment).  The prefetcher's copy-stream probe runs without augmentation and consumes no draw; evaluation never augments.
     ``args.model_ema`` (a util.model_ema.DeviceModelEma built on this model): ``update()`` after every optimizer update -- once per
     ``accum_iter`` micro-batches, on the compute stream behind the AdamW launch, outside the captured graph -- whether or not the overflow
     guard skipped that update."""
@@ -860,6 +914,7 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     optimizer = as_fused(optimizer, model)
     eraser = _device_erasing(args, cube_default=_video)
     cropper = _device_crop(args, "device_crop", DeviceRandomResizedCrop, getattr(model, "module", model), video=_video)
+    augmenter = _device_randaug(args)
     if loss_scaler is not None and hasattr(loss_scaler, "bind"):
         loss_scaler.bind(optimizer)
     accum_iter = max(1, int(getattr(args, "accum_iter", 1) or 1)) if args is not None else 1
@@ -877,8 +932,12 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     lr = optimizer.param_groups[0]["lr"]
     # batch i+1 travels host -> device on a copy stream while step i runs (DevicePrefetcher); the reference's loop copies on the compute stream
     for it, samples, targets, extra in DevicePrefetcher(data_loader, device, _copy_stream_picker(model, criterion, cropper=cropper)):
+        if augmenter is not None and _video:   # RandAugment on the source byte clips, in front of the crop (the reference's order)
+            samples = _randaug_clip_batch(m, augmenter, samples, cropper is not None)
         if cropper is not None:   # the source batch becomes the 224 x 224 byte batch, on the compute stream, in front of the step
             samples = _resample_batch(m, cropper, samples)
+        if augmenter is not None and not _video:   # RandAugment on the cropped and flipped byte batch (timm's order)
+            samples = _randaug_image_batch(m, augmenter, samples)
         # parity tests may append the random draws to inject: (samples, targets, (g1, g2), keep_mask)
         gumbel = tuple(t.to(device).contiguous() for t in extra[0]) if len(extra) > 0 and extra[0] is not None else None
         keep_mask = extra[1].to(device).contiguous() if len(extra) > 1 and extra[1] is not None else None

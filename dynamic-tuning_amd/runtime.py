@@ -812,6 +812,65 @@ class DyTEngine:
             self._rc_events[k].record()
         return resample_clip_f32(clips, self._rc_dev, None, out=self._rc_out[:draw.units], norm=self.input_norm, units=draw.units)
 
+    # ---- RandAugment on byte clips and images --------------------------------------------------------
+    def randaug(self, pixels, sizes, draw):
+        """dyt_randaug_u8 on torch's current stream: the uint8 device batch ``pixels`` -- clips [B, T, Hs, Ws, 3] or images [B, Hs, Ws, 3],
+        channels last, padded -- augmented as ``draw`` (a util.randaug.AugDraw, e.g. ``DeviceRandAugment.draw_for(sizes)``) says -> new
+        bytes of the same shape; ``pixels`` is not written.  ``sizes`` (host, [B, 2] = the valid height and width, or None): compared with
+        the draw's.  Like ``resample``: ONE static device table (rows for max_batch units of 8 layers), a small pinned host ring and a
+        non-blocking copy on the current stream.  The destination, work and histogram buffers are the engine's, sized by the largest batch
+        seen: the returned batch is valid until the next call.  Nothing is allocated before the first call."""
+        from _lib import RANDAUG_HIST_WORDS, RANDAUG_MAX_LAYERS, randaug_u8
+        from util.randaug import table_words
+        if not hasattr(self.L, "dyt_randaug_u8"):
+            raise DyTError("this libdyt_hip has no dyt_randaug_u8 (device RandAugment): rebuild it")
+        if not (torch.is_tensor(pixels) and pixels.dtype == torch.uint8 and pixels.dim() in (4, 5) and pixels.shape[-1] == 3):
+            raise DyTError("randaug takes a uint8 batch of clips [B, T, Hs, Ws, 3] or images [B, Hs, Ws, 3], channels last (got %s %s)" % (
+                getattr(pixels, "dtype", type(pixels)), tuple(getattr(pixels, "shape", ()))))
+        n, t = int(pixels.shape[0]), (int(pixels.shape[1]) if pixels.dim() == 5 else 1)
+        cap = max(1, int(self.cfg.max_batch) // t)
+        if draw.units != n:
+            raise DyTError("randaug: the draw holds %d units, the batch %d" % (draw.units, n))
+        if n > cap:
+            raise DyTError("randaug: the batch has %d units of %d frame(s), the engine's max_batch is %d frames" % (n, t, int(self.cfg.max_batch)))
+        if sizes is not None:
+            given = [tuple(int(v) for v in r) for r in (sizes.tolist() if hasattr(sizes, "tolist") else sizes)]
+            if given != draw.sizes():
+                raise DyTError("randaug: the draw was made for other sizes than the batch's")
+        try:
+            draw.check(int(pixels.shape[-3]), int(pixels.shape[-2]))   # an invalid row is refused before upload (the device would write zeros)
+        except ValueError as e:
+            raise DyTError(str(e))
+        words = draw.words(cap)
+        if getattr(self, "_ra_dev", None) is None:
+            full = table_words(cap, RANDAUG_MAX_LAYERS)
+            self._ra_dev = torch.zeros(full, dtype=torch.int32, device=self.device)
+            self._ra_ring = torch.zeros(self.MIX_RING, full, dtype=torch.int32).pin_memory()
+            self._ra_events = [None] * self.MIX_RING
+            self._ra_at = 0
+            self._ra_out = self._ra_work = self._ra_stats = None
+        pixels = pixels.contiguous()
+        nbytes = pixels.numel()
+        if self._ra_out is None or self._ra_out.numel() < nbytes:
+            self._ra_out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ra_work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self._ra_stats is None or self._ra_stats.numel() < n * t * RANDAUG_HIST_WORDS:
+            self._ra_stats = torch.empty(n * t * RANDAUG_HIST_WORDS, dtype=torch.int32, device=self.device)
+        k = self._ra_at
+        self._ra_at = (k + 1) % self.MIX_RING
+        if self._ra_events[k] is not None:
+            self._ra_events[k].synchronize()   # the copy that read this slot MIX_RING draws ago: long complete, this does not wait
+        nw = len(words) // 4
+        self._ra_ring[k, :nw].copy_(torch.frombuffer(bytearray(words), dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            self._ra_dev[:nw].copy_(self._ra_ring[k, :nw], non_blocking=True)
+            if self._ra_events[k] is None:
+                self._ra_events[k] = torch.cuda.Event()
+            self._ra_events[k].record()
+        table = self._ra_dev[:table_words(cap, draw.layers)]
+        return randaug_u8(pixels, table, None, out=self._ra_out[:nbytes].view(pixels.shape), work=self._ra_work[:nbytes].view(pixels.shape),
+                          stats=self._ra_stats, layers=draw.layers, launch_mask=draw.launch_mask())
+
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on):
         self._ck(self.L.dyt_profile_enable(self.h, 1 if on else 0))

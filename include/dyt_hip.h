@@ -503,6 +503,28 @@ int dyt_resample_clip_f32(const uint8_t* src, int batch, int frames, int src_h, 
  * window positions.  An invalid row gives zeros (the row's src word is not checked here: no source is read).  One launch on `stream`. */
 int dyt_resample_clip_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream);
 
+/* RandAugment on the device for byte clips and images (csrc/randaug.h, csrc/randaug.hip): the reference's video_datasets/rand_augment.py
+ * -- Pillow's 8-bit arithmetic behind it -- restated byte for byte as twelve operations: Identity, Invert, Solarize, SolarizeAdd, Posterize,
+ * AutoContrast, Equalize (3 x 256 tables), Brightness, Color, Contrast (Image.blend against a degenerate value, fp32), Sharpness (blend
+ * against ImageFilter.SMOOTH) and Affine (Image.transform with a fill colour, bilinear or bicubic, fp64).  Two context-free entries, added
+ * without an ABI version change (the version stays 5) and discovered by their symbols; the same bytes from both libraries.
+ * dyt_randaug_u8: src uint8 [units, frames, src_h, src_w, 3] (clips padded to one shape; an image batch is frames = 1) -> dst of the same
+ * shape; work is a third buffer of that shape and stats int32 [units * frames * 1024] (all 16-byte aligned, all distinct).  table_dev:
+ * 16 header words (magic 0x31475541, units, layers) and 20-word rows [layers][capacity], one per (layer, unit): op, the unit's valid h and
+ * w, an integer argument, filter (2 bilinear, 3 bicubic), fill (r | g << 8 | b << 16), an fp32 factor, the buffers the row reads and writes
+ * (source | destination << 8; 0 src, 1 dst, 2 work) and six fp64 coefficients.  All frames of a unit share its rows.  Layers run one after
+ * another on `stream`; layer 0 reads src, pixel-local operations may work in place, Sharpness and Affine write the buffer they do not read,
+ * the last layer writes dst.  Bytes outside a unit's valid h x w arrive in dst unchanged.  launch_mask (HOST memory, one word per layer, or
+ * null = everything): bits 0..3 = some unit of the layer runs a table / blend / Sharpness / Affine operation, bit 4 = some unit needs the
+ * frame histograms (AutoContrast, Equalize, Contrast); only what is named is launched.  Nothing of a row is used before it is checked; a unit
+ * with an invalid row in any layer, a buffer sequence that does not link, or no row is written as ZEROS.  The table is read when the kernels
+ * RUN.  Refused with a text, before anything is enqueued: null or misaligned pointers, src == dst (or work equal to either), units / frames /
+ * layers < 1, layers > 8, units * frames > 65535, units > capacity, a side < 1 or above 4096. */
+int dyt_randaug_u8(const uint8_t* src, int units, int frames, int src_h, int src_w, uint8_t* dst, uint8_t* work, int32_t* stats, const void* table_dev, int capacity, int layers, const uint32_t* launch_mask, void* stream);
+/* Debug / test entry: the 3 x 256 table (table operations; the identity otherwise) and the Contrast constant that (unit, frame, layer)
+ * uses when `src` is that layer's input -> out_dev int32 [769] (16-byte aligned).  An invalid unit gives zeros.  Overwrites stats. */
+int dyt_randaug_table(const uint8_t* src, int units, int frames, int src_h, int src_w, int32_t* stats, const void* table_dev, int capacity, int layers, int unit, int frame, int layer, int32_t* out_dev, void* stream);
+
 /* Streaming evaluation statistics (csrc/eval_stats.h, csrc/eval_stats.hip): a batch of logits, labels and token masks is folded into a
  * fixed-size device-resident state, so that an evaluation loop keeps no per-sample tensor.  Two context-free entries, added without an ABI
  * version change (the version stays 5) and discovered by their symbols; pure fp32 / integer, the same bits from both libraries.
