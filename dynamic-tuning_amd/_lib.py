@@ -358,6 +358,51 @@ def resample_coeffs(table, row, src_h, src_w):
     return out
 
 
+RESAMPLE_WIDE_KMAX, RESAMPLE_WIDE_COEFF_WORDS, RESAMPLE_WIDE_ROW_BYTES = 75, 2 * 77 * 224, 672   # csrc/resample_wide.h
+
+
+def resample_wide_u8(pixels, table, draw=None, out=None, scratch=None):
+    """dyt_resample_wide_u8: ``resample_u8`` at any downscale -- the same table, layouts and bits, without the bound of a box being at most
+    2.5 times the size it is resized to (up to 75 taps per position; csrc/resample_wide.h).  ``draw``: checked on the host first, as a wide
+    draw.  ``scratch``: an int32 device buffer of dyt_resample_wide_scratch_bytes(B, Hs) bytes at least (coefficients and the intermediate
+    rows), allocated here when absent."""
+    import torch
+    L = lib()
+    n, hs, ws, capacity = _resample_args(L, pixels, table)
+    if not hasattr(L, "dyt_resample_wide_u8") or not hasattr(L, "dyt_resample_wide_scratch_bytes"):
+        raise DyTError("this libdyt_hip has no dyt_resample_wide_u8 (device crop / resize at any downscale): rebuild it")
+    if draw is not None:
+        if draw.units != n:
+            raise DyTError("resample: the draw holds %d images, the batch %d" % (draw.units, n))
+        try:
+            draw.check(hs, ws, wide=True)
+        except ValueError as e:
+            raise DyTError(str(e))
+    pixels = pixels.contiguous()
+    if out is None:
+        out = torch.empty(n, 224, 224, 3, device=pixels.device, dtype=torch.uint8)
+    if scratch is None:
+        scratch = torch.empty(int(L.dyt_resample_wide_scratch_bytes(n, hs)) // 4, device=pixels.device, dtype=torch.int32)
+    with torch.cuda.device(pixels.device):
+        check(L.dyt_resample_wide_u8(ptr(pixels), n, hs, ws, ptr(out), ptr(table), capacity, ptr(scratch),
+                                     scratch.numel() * scratch.element_size(), stream_ptr()), L)
+    return out
+
+
+def resample_wide_coeffs(table, row, src_h, src_w):
+    """dyt_resample_wide_coeffs: the coefficient tables the wide kernels compute for table row ``row`` of a batch padded to src_h x src_w
+    -> int32 [2, 77, 224] on the device (axis 0 = output rows, 1 = columns; first tap, tap count, 75 coefficients per window position)."""
+    import torch
+    L = lib()
+    if not hasattr(L, "dyt_resample_wide_coeffs"):
+        raise DyTError("this libdyt_hip has no dyt_resample_wide_coeffs (device crop / resize at any downscale): rebuild it")
+    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    out = torch.zeros(2, 2 + RESAMPLE_WIDE_KMAX, 224, device=table.device, dtype=torch.int32)
+    with torch.cuda.device(table.device):
+        check(L.dyt_resample_wide_coeffs(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
+    return out
+
+
 RESAMPLE_BILINEAR_F32, RESAMPLE_CLIP_COEFF_WORDS = 2, 2 * 4 * 224   # csrc/resample_clip.h
 IMAGENET_NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 
@@ -631,6 +676,9 @@ SYMBOLS = {
     "dyt_resample_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp]),
     "dyt_resample_scratch_bytes": (_i64, [_i]),
     "dyt_resample_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "dyt_resample_wide_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp]),
+    "dyt_resample_wide_scratch_bytes": (_i64, [_i, _i]),
+    "dyt_resample_wide_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dyt_resample_clip_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _vp]),
     "dyt_resample_clip_coeffs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dyt_randaug_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_uint32), _vp]),
@@ -705,6 +753,7 @@ SYMBOLS = {
 # build behind DYT_LIB_DIR) still loads; the caller that needs the entry refuses by name (runtime.DyTEngine.adamw_segments).
 OPTIONAL_SYMBOLS = {"dyt_adamw_segments", "dyt_set_input_norm", "dyt_normalize_u8", "dyt_set_mix", "dyt_mix_images", "dyt_mix_targets",
                     "dyt_set_erase", "dyt_erase_images", "dyt_resample_u8", "dyt_resample_scratch_bytes", "dyt_resample_coeffs",
+                    "dyt_resample_wide_u8", "dyt_resample_wide_scratch_bytes", "dyt_resample_wide_coeffs",
                     "dyt_resample_clip_f32", "dyt_resample_clip_coeffs", "dyt_randaug_u8", "dyt_randaug_table",
                     "dyt_eval_rows", "dyt_eval_keep", "dyt_unit_bwd_prep", "dyt_unit_ln_bwd", "dyt_unit_ln_param_grad", "dyt_unit_tok_bwd",
                     "dyt_unit_gate", "dyt_unit_gather_index", "dyt_unit_ln_gather", "dyt_unit_ln_fwd", "dyt_unit_adapter_ln_fwd", "dyt_unit_ln_cls",

@@ -20,7 +20,7 @@ from _lib import DyTError
 from util.mixup import DeviceMixup
 from util.erasing import DeviceRandomErasing
 from util.crop import (DeviceClipRandomResizedCrop, DeviceClipScaleJitterCrop, DeviceClipUniformCrop, DeviceRandomResizedCrop,
-                       DeviceResizeCenterCrop, _DeviceClipCrop, full_clip_sizes, full_sizes, probe_clip_draw, probe_draw)
+                       DeviceResize, DeviceResizeCenterCrop, _DeviceClipCrop, full_clip_sizes, full_sizes, probe_clip_draw, probe_draw)
 from util.metrics import StreamingEval, accuracy, mean_per_class_accuracy
 from util.model_ema import DeviceModelEma
 from util.randaug import DeviceRandAugment
@@ -763,7 +763,7 @@ def _device_crop(args, name, kind, model, video=False):
         return None
     clip_kinds = (DeviceClipUniformCrop,) if name == "device_eval_crop" else (DeviceClipScaleJitterCrop, DeviceClipRandomResizedCrop)
     if video:
-        if isinstance(cropper, (DeviceRandomResizedCrop, DeviceResizeCenterCrop)):
+        if isinstance(cropper, (DeviceRandomResizedCrop, DeviceResizeCenterCrop, DeviceResize)):
             raise DyTError("args.%s: video clips are not implemented by util.crop.%s (images only); a clip loop takes util.crop.%s" % (
                 name, type(cropper).__name__, " / ".join(k.__name__ for k in clip_kinds)))
         if not isinstance(cropper, clip_kinds):
@@ -771,8 +771,8 @@ def _device_crop(args, name, kind, model, video=False):
     else:
         if isinstance(cropper, _DeviceClipCrop):
             raise DyTError("args.%s: util.crop.%s crops video clips; an image loop takes a util.crop.%s" % (name, type(cropper).__name__, kind.__name__))
-        if not isinstance(cropper, kind):
-            raise DyTError("args.%s must be a util.crop.%s (got %r)" % (name, kind.__name__, type(cropper)))
+        if not isinstance(cropper, (kind, DeviceResize)):   # DeviceResize: the pipeline without augmentation, train and val alike
+            raise DyTError("args.%s must be a util.crop.%s or a util.crop.DeviceResize (got %r)" % (name, kind.__name__, type(cropper)))
     if getattr(model, "input_norm", None) is None:
         raise DyTError("args.%s: the source batch is uint8, so the model must be built with input_norm (the mean / std the byte path "
                        "normalises with)" % name)
@@ -793,7 +793,7 @@ def _resample_batch(model, cropper, samples, probe=False):
     if sizes is None:
         sizes = full_sizes(pixels)
     eng = model.engine(pixels.shape[0], pixels.device)
-    draw = probe_draw(sizes) if probe else cropper.draw_for(sizes)
+    draw = probe_draw(sizes, wide=getattr(cropper, "any_scale", False)) if probe else cropper.draw_for(sizes)
     return eng.resample(pixels.contiguous(), sizes, draw)
 
 

@@ -726,11 +726,17 @@ class DyTEngine:
         DYT_F_IMAGES_U8 | DYT_F_IMAGES_NHWC reads.  ``sizes`` (host, [B, 2] = the images' valid height and width, or None): compared
         with the draw's.  Like ``set_erase``: ONE static device table (a row for each of max_batch images), a small pinned host ring and a
         non-blocking copy on the current stream -- the kernels read the table when they run, so a captured graph around them serves every
-        draw.  The scratch and output buffers are the engine's: the returned batch is valid until the next call."""
-        from _lib import resample_u8
+        draw.  The scratch and output buffers are the engine's: the returned batch is valid until the next call.  A WIDE draw
+        (``draw.wide``: ``any_scale=True`` of the util.crop classes) always takes dyt_resample_wide_u8, even when every row would fit the
+        11-tap kernels, so the launches of an any_scale loop do not depend on the draw; its scratch (coefficients and the intermediate
+        rows of max_batch images of the batch's padded height) is allocated on first use and only ever grows."""
+        from _lib import resample_u8, resample_wide_u8
         from util.crop import table_words
         if not hasattr(self.L, "dyt_resample_u8"):
             raise DyTError("this libdyt_hip has no dyt_resample_u8 (device crop / resize): rebuild it")
+        wide = bool(getattr(draw, "wide", False))
+        if wide and not (hasattr(self.L, "dyt_resample_wide_u8") and hasattr(self.L, "dyt_resample_wide_scratch_bytes")):
+            raise DyTError("this libdyt_hip has no dyt_resample_wide_u8 (device crop / resize at any downscale): rebuild it")
         n = int(pixels.shape[0])
         cap = int(self.cfg.max_batch)
         if draw.units != n:
@@ -763,6 +769,11 @@ class DyTEngine:
             if self._rs_events[k] is None:
                 self._rs_events[k] = torch.cuda.Event()
             self._rs_events[k].record()
+        if wide:
+            need = int(self.L.dyt_resample_wide_scratch_bytes(cap, int(pixels.shape[1]))) // 4
+            if getattr(self, "_rsw_scratch", None) is None or self._rsw_scratch.numel() < need:
+                self._rsw_scratch = torch.empty(need, dtype=torch.int32, device=self.device)
+            return resample_wide_u8(pixels, self._rs_dev, None, out=self._rs_out[:n], scratch=self._rsw_scratch)
         return resample_u8(pixels, self._rs_dev, None, out=self._rs_out[:n], scratch=self._rs_scratch)
 
     def resample_clip(self, clips, sizes, draw):

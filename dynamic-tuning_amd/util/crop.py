@@ -42,9 +42,12 @@ def table_words(capacity):
     return HEADER_WORDS + ROW_WORDS * int(capacity)
 
 
-def row_error(row, batch_h=None, batch_w=None):
-    """csrc/resample.h's resample_row_ok as a text (None: the row is valid)."""
+def row_error(row, batch_h=None, batch_w=None, wide=False):
+    """csrc/resample.h's resample_row_ok as a text (None: the row is valid).  ``wide``: csrc/resample_wide.h's resample_wide_row_ok -- the
+    same conditions without the bound of 2.5 (a side is at most 4096, which bounds the taps by 75)."""
     sh, sw, top, left, bh, bw, fh, fw, oy, ox, flags = row
+    if wide and (sh > MAX_SIDE or sw > MAX_SIDE):
+        return "the valid extent %d x %d has a side above %d" % (sh, sw, MAX_SIDE)
     if sh < 1 or sw < 1:
         return "the valid extent %d x %d is empty" % (sh, sw)
     if (batch_h is not None and sh > batch_h) or (batch_w is not None and sw > batch_w):
@@ -57,7 +60,7 @@ def row_error(row, batch_h=None, batch_w=None):
         return "the resized image %d x %d is smaller than the %d x %d window" % (fh, fw, OUT, OUT)
     if oy < 0 or ox < 0 or oy + OUT > fh or ox + OUT > fw:
         return "the window (offset %d, %d) lies outside the resized image %d x %d" % (oy, ox, fh, fw)
-    if 2 * bh > 5 * fh or 2 * bw > 5 * fw:
+    if not wide and (2 * bh > 5 * fh or 2 * bw > 5 * fw):
         return ("the box %d x %d is more than 2.5 times the resized image %d x %d (the kernels take at most 11 taps): decode to a smaller "
                 "size" % (bh, bw, fh, fw))
     return None
@@ -92,11 +95,15 @@ class CropDraw:
     """The host-side parameters of one batch: per image the row ``(src_h, src_w, top, left, box_h, box_w, full_h, full_w, off_y, off_x,
     flags)`` of csrc/resample.h.  ``words(capacity)`` is the table the kernels read.  With ``filter=BILINEAR_F32`` the rows are CLIP rows
     (csrc/resample_clip.h): a 12th word ``src`` names the source clip a row reads, output unit r is written from row r, and the rows are
-    checked with ``clip_row_error``."""
+    checked with ``clip_row_error``.  ``wide``: a draw for the wide-tap kernels (csrc/resample_wide.h) -- the same table, its rows checked
+    without the bound of 2.5; the engine resamples a wide draw with dyt_resample_wide_u8, whatever its rows."""
 
-    def __init__(self, rows, filter=BICUBIC):
+    def __init__(self, rows, filter=BICUBIC, wide=False):
         self.rows = [tuple(int(v) for v in r) for r in rows]
         self.filter = int(filter)
+        self.wide = bool(wide)
+        if self.wide and self.filter != BICUBIC:
+            raise ValueError("resample: wide=True is a draw of image rows (clip rows have no scale bound)")
         if self.filter not in (BICUBIC, BILINEAR_F32):
             raise ValueError("resample: filter %r is not implemented (3 = Pillow's bicubic on bytes, 2 = torch's float bilinear on clips)" % (filter,))
         if not self.rows:
@@ -122,10 +129,12 @@ class CropDraw:
         """The source image / clip of every row (a bicubic row reads the image of its own number)."""
         return [r[11] for r in self.rows] if self.clip else list(range(len(self.rows)))
 
-    def check(self, batch_h=None, batch_w=None, batch=None):
-        """The refusal of an invalid row, made where the values are still on the host (the device would write such an image as zeros)."""
+    def check(self, batch_h=None, batch_w=None, batch=None, wide=None):
+        """The refusal of an invalid row, made where the values are still on the host (the device would write such an image as zeros).
+        ``wide`` (None: the draw's own): check the rows for the wide-tap kernels."""
+        wide = self.wide if wide is None else bool(wide)
         for i, r in enumerate(self.rows):
-            e = clip_row_error(r, batch, batch_h, batch_w) if self.clip else row_error(r, batch_h, batch_w)
+            e = clip_row_error(r, batch, batch_h, batch_w) if self.clip else row_error(r, batch_h, batch_w, wide=wide)
             if e:
                 raise ValueError("resample: %s %d: %s" % ("unit" if self.clip else "image", i, e))
 
@@ -148,7 +157,7 @@ class CropDraw:
         return b"".join(out)
 
     def __repr__(self):
-        return "CropDraw(%r%s)" % (self.rows, ", filter=%d" % self.filter if self.clip else "")
+        return "CropDraw(%r%s%s)" % (self.rows, ", filter=%d" % self.filter if self.clip else "", ", wide=True" if self.wide else "")
 
 
 def _sizes_list(sizes):
@@ -178,20 +187,22 @@ class _DeviceCrop:
     def __call__(self, pixels, sizes=None):
         """The cropped byte batch uint8 [B, 224, 224, 3] of a device batch uint8 [B, Hs, Ws, 3]; ``sizes`` [B, 2] (host) = the images' valid
         (height, width), None: every image fills the batch's shape."""
-        from _lib import resample_u8
+        from _lib import resample_u8, resample_wide_u8
         import torch
         d = self.draw_for(full_sizes(pixels) if sizes is None else sizes)
         if d.units != int(pixels.shape[0]):
             raise ValueError("resample: %d sizes for a batch of %d images" % (d.units, int(pixels.shape[0])))
         table = torch.frombuffer(bytearray(d.words()), dtype=torch.int32).to(pixels.device)
-        return resample_u8(pixels, table, d)
+        return (resample_wide_u8 if d.wide else resample_u8)(pixels, table, d)
 
 
 class DeviceRandomResizedCrop(_DeviceCrop):
     """The reference RandomResizedCrop's arguments plus ``flip`` (RandomHorizontalFlip's p; None: no flip stage) and ``generator`` (a
-    torch.Generator; None: torch's global one, as the reference).  Only what the kernels implement is accepted: size 224, bicubic."""
+    torch.Generator; None: torch's global one, as the reference).  Only what the kernels implement is accepted: size 224, bicubic.
+    ``any_scale``: the draws are wide draws (the wide-tap kernels, csrc/resample_wide.h): the same boxes from the same random numbers, and
+    a box may be any multiple of 224 instead of at most 2.5 times."""
 
-    def __init__(self, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation=3, flip=0.5, generator=None):
+    def __init__(self, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation=3, flip=0.5, generator=None, any_scale=False):
         if isinstance(size, (tuple, list)):
             size = size[0] if len(size) == 1 or (len(size) == 2 and size[0] == size[1]) else size
         if size != OUT:
@@ -203,6 +214,7 @@ class DeviceRandomResizedCrop(_DeviceCrop):
         if flip is not None and not (0.0 <= float(flip) <= 1.0):
             raise ValueError("DeviceRandomResizedCrop: flip is a probability or None")
         self.size, self.scale, self.ratio, self.interpolation, self.flip, self.generator = OUT, tuple(scale), tuple(ratio), BICUBIC, flip, generator
+        self.any_scale = bool(any_scale)
         self._injected = []
 
     def inject(self, draws):
@@ -241,21 +253,22 @@ class DeviceRandomResizedCrop(_DeviceCrop):
             i, j, h, w = self.get_params(sh, sw)
             mirror = bool(torch.rand(1, generator=self.generator) < self.flip) if self.flip is not None else False
             rows.append((sh, sw, i, j, h, w, OUT, OUT, 0, 0, FLAG_MIRROR if mirror else 0))
-        return CropDraw(rows)
+        return CropDraw(rows, wide=self.any_scale)
 
 
 class DeviceResizeCenterCrop(_DeviceCrop):
     """``Resize(resize, interpolation=3)`` + ``CenterCrop(size)`` of torchvision: the short side becomes ``resize``, the long side
-    ``int(resize * long / short)``; the window starts at ``int(round((full - size) / 2.0))``.  Makes no draw."""
+    ``int(resize * long / short)``; the window starts at ``int(round((full - size) / 2.0))``.  Makes no draw.  ``any_scale``: wide draws
+    (csrc/resample_wide.h), so a short side above 2.5 x ``resize`` is taken."""
 
-    def __init__(self, resize=256, size=224, interpolation=3):
+    def __init__(self, resize=256, size=224, interpolation=3, any_scale=False):
         if size != OUT:
             raise NotImplementedError("DeviceResizeCenterCrop: size=%r is not implemented (the kernels write 224 x 224)" % (size,))
         if getattr(interpolation, "value", interpolation) not in (BICUBIC, "bicubic"):
             raise NotImplementedError("DeviceResizeCenterCrop: interpolation=%r is not implemented (3 = bicubic only)" % (interpolation,))
         if int(resize) != resize or resize < OUT:
             raise ValueError("DeviceResizeCenterCrop: resize is an integer >= %d (the window must fit), got %r" % (OUT, resize))
-        self.resize, self.size = int(resize), OUT
+        self.resize, self.size, self.any_scale = int(resize), OUT, bool(any_scale)
 
     def geometry(self, height, width):
         """(full_h, full_w, off_y, off_x)"""
@@ -270,13 +283,30 @@ class DeviceResizeCenterCrop(_DeviceCrop):
         for (sh, sw) in _sizes_list(sizes):
             fh, fw, oy, ox = self.geometry(sh, sw)
             rows.append((sh, sw, 0, 0, sh, sw, fh, fw, oy, ox, 0))
-        return CropDraw(rows)
+        return CropDraw(rows, wide=self.any_scale)
 
 
-def probe_draw(sizes):
+class DeviceResize(_DeviceCrop):
+    """``Resize((224, 224), interpolation=3)`` of torchvision, the reference's pipeline without augmentation (datasets/image_datasets_noaug.py,
+    train and val): the whole image resized to 224 x 224, each axis with its own scale factor.  Makes no draw.  ``any_scale``: wide draws
+    (csrc/resample_wide.h), so a side above 560 is taken."""
+
+    def __init__(self, size=(OUT, OUT), interpolation=3, any_scale=False):
+        if not isinstance(size, (tuple, list)) or tuple(size) != (OUT, OUT):   # an int is torchvision's short-side rule: DeviceResizeCenterCrop's
+            raise NotImplementedError("DeviceResize: size=%r is not implemented ((224, 224) only: the kernels write 224 x 224)" % (size,))
+        if getattr(interpolation, "value", interpolation) not in (BICUBIC, "bicubic"):
+            raise NotImplementedError("DeviceResize: interpolation=%r is not implemented (3 = bicubic only)" % (interpolation,))
+        self.size, self.interpolation, self.any_scale = (OUT, OUT), BICUBIC, bool(any_scale)
+
+    def draw_for(self, sizes):
+        return CropDraw([(sh, sw, 0, 0, sh, sw, OUT, OUT, 0, 0, 0) for (sh, sw) in _sizes_list(sizes)], wide=self.any_scale)
+
+
+def probe_draw(sizes, wide=False):
     """A valid draw that consumes no random number (the top-left 224 x 224 of every image, or the whole of a smaller one): for the loop's
-    one-off stream probe, which needs a batch of the step's shape and must leave the generators alone."""
-    return CropDraw([(sh, sw, 0, 0, min(sh, OUT), min(sw, OUT), OUT, OUT, 0, 0, 0) for (sh, sw) in _sizes_list(sizes)])
+    one-off stream probe, which needs a batch of the step's shape and must leave the generators alone.  ``wide``: a wide draw, so that the
+    probe of an ``any_scale`` loop takes the launches its steps take."""
+    return CropDraw([(sh, sw, 0, 0, min(sh, OUT), min(sw, OUT), OUT, OUT, 0, 0, 0) for (sh, sw) in _sizes_list(sizes)], wide=wide)
 
 
 def pad_collate(batch, pad_to=None):

@@ -480,6 +480,22 @@ int64_t dyt_resample_scratch_bytes(int batch);
  * the 224 window positions.  An invalid row gives zeros.  One launch on `stream`. */
 int dyt_resample_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream);
 
+/* The same crop / resize at ANY downscale (csrc/resample_wide.h, csrc/resample_wide.hip): the table, the filter, the rounding and the
+ * layouts of dyt_resample_u8, without its bound of box <= 2.5 full.  A row is valid under every other condition of dyt_resample_u8; a box
+ * side is at most 4096 and full at least 224, so a window position takes at most 75 taps.  Three context-free entries, added without an
+ * ABI version change (the version stays 5) and discovered by their symbols; the same bits from both libraries, and for every row
+ * dyt_resample_u8 takes, its bits.
+ * dyt_resample_wide_u8: scratch_dev holds dyt_resample_wide_scratch_bytes(batch, src_h) bytes at least, 16-byte aligned: the coefficient
+ * tables (137 984 bytes per image), then the horizontally resampled source rows, uint8 [batch][src_h][672].  Three launches on `stream`
+ * whose grids depend on (batch, src_h, src_w) alone: coefficients, a horizontal pass over the source rows the window's vertical taps need
+ * (each filtered once), a vertical pass over the intermediate.  An invalid row is written as ZEROS.  The padding of the source never
+ * reaches an output.  Refused with a text, before anything is enqueued: what dyt_resample_u8 refuses. */
+int dyt_resample_wide_u8(const uint8_t* src, int batch, int src_h, int src_w, uint8_t* dst, const void* table_dev, int capacity, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int64_t dyt_resample_wide_scratch_bytes(int batch, int src_h);
+/* Debug / test entry: dyt_resample_coeffs of the wide route -> out_dev int32 [2][77][224] (16-byte aligned): per axis the first tap, the tap
+ * count and 75 coefficients of each of the 224 window positions.  An invalid row gives zeros.  One launch on `stream`. */
+int dyt_resample_wide_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream);
+
 /* Device clip pipeline from byte clips (csrc/resample_clip.h, csrc/resample_clip.hip): short-side scale jitter + random crop, random resized
  * crop, uniform one- / three-view crops and the mirror of the video loaders, as ONE two-tap resample of normalised frames --
  * torch.nn.functional.interpolate(x, size, mode='bilinear', align_corners=False) restated bit for bit: per axis scale = (float)box / (float)full,
