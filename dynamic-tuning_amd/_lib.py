@@ -301,10 +301,14 @@ def erase_images(images, table, frames=1, norm=None, mix_params=None, out=None):
 RESAMPLE_HEADER_WORDS, RESAMPLE_ROW_WORDS, RESAMPLE_COEFF_WORDS, RESAMPLE_MAX_SIDE = 16, 12, 2 * 13 * 224, 4096   # csrc/resample.h
 
 
-def _resample_args(L, pixels, table):
+def _resample_bicubic(entry, feature, wide, pixels, table, draw, out, scratch):
+    """The body of ``resample_u8`` (entry dyt_resample_u8) and ``resample_wide_u8`` (dyt_resample_wide_u8, ``wide``): the argument check, the
+    draw check, the scratch sizing and the call."""
     import torch
-    if not hasattr(L, "dyt_resample_u8"):
-        raise DyTError("this libdyt_hip has no dyt_resample_u8 (device crop / resize): rebuild it")
+    L = lib()
+    sizer = entry[:-2] + "scratch_bytes"   # dyt_resample_scratch_bytes / dyt_resample_wide_scratch_bytes
+    if not (hasattr(L, entry) and hasattr(L, sizer)):
+        raise DyTError("this libdyt_hip has no %s (%s): rebuild it" % (entry, feature))
     if not (torch.is_tensor(pixels) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 4 and pixels.shape[3] == 3):
         raise DyTError("resample takes a uint8 device batch [B, Hs, Ws, 3] (got %s %s); planar sources and clips are not implemented" % (
             getattr(pixels, "dtype", type(pixels)), tuple(getattr(pixels, "shape", ()))))
@@ -314,7 +318,37 @@ def _resample_args(L, pixels, table):
     if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and
             table.numel() >= RESAMPLE_HEADER_WORDS + RESAMPLE_ROW_WORDS * n):
         raise DyTError("resample table: a contiguous int32 device tensor of 16 + 12 x %d words at least (util.crop.CropDraw.words(capacity))" % n)
-    return n, hs, ws, (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    if draw is not None:
+        if draw.units != n:
+            raise DyTError("resample: the draw holds %d images, the batch %d" % (draw.units, n))
+        try:
+            draw.check(hs, ws, wide=True) if wide else draw.check(hs, ws)
+        except ValueError as e:
+            raise DyTError(str(e))
+    pixels = pixels.contiguous()
+    if out is None:
+        out = torch.empty(n, 224, 224, 3, device=pixels.device, dtype=torch.uint8)
+    if scratch is None:
+        need = int(getattr(L, sizer)(n, hs) if wide else getattr(L, sizer)(n))
+        scratch = torch.empty(need // 4, device=pixels.device, dtype=torch.int32)
+    with torch.cuda.device(pixels.device):
+        check(getattr(L, entry)(ptr(pixels), n, hs, ws, ptr(out), ptr(table), capacity, ptr(scratch), scratch.numel() * scratch.element_size(),
+                                stream_ptr()), L)
+    return out
+
+
+def _resample_coeffs(entry, feature, fields, table, row, src_h, src_w):
+    """The body of the three ``*_coeffs`` wrappers: entry ``entry`` for table row ``row`` -> int32 [2, fields, 224] on the device."""
+    import torch
+    L = lib()
+    if not hasattr(L, entry):
+        raise DyTError("this libdyt_hip has no %s (%s): rebuild it" % (entry, feature))
+    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
+    out = torch.zeros(2, fields, 224, device=table.device, dtype=torch.int32)
+    with torch.cuda.device(table.device):
+        check(getattr(L, entry)(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
+    return out
 
 
 def resample_u8(pixels, table, draw=None, out=None, scratch=None):
@@ -322,40 +356,13 @@ def resample_u8(pixels, table, draw=None, out=None, scratch=None):
     and mirrored as the rows of the device table ``table`` (int32 words: csrc/resample.h, util.crop.CropDraw.words()) say -> uint8
     [B, 224, 224, 3], on torch's current stream.  ``draw`` (the CropDraw behind the table): checked against the batch's shape on the host
     first -- an invalid row is refused here; the device would write that image as zeros.  ``out`` / ``scratch``: buffers to use."""
-    import torch
-    L = lib()
-    n, hs, ws, capacity = _resample_args(L, pixels, table)
-    if draw is not None:
-        if draw.units != n:
-            raise DyTError("resample: the draw holds %d images, the batch %d" % (draw.units, n))
-        try:
-            draw.check(hs, ws)
-        except ValueError as e:
-            raise DyTError(str(e))
-    pixels = pixels.contiguous()
-    if out is None:
-        out = torch.empty(n, 224, 224, 3, device=pixels.device, dtype=torch.uint8)
-    need = int(L.dyt_resample_scratch_bytes(n))
-    if scratch is None:
-        scratch = torch.empty(need // 4, device=pixels.device, dtype=torch.int32)
-    with torch.cuda.device(pixels.device):
-        check(L.dyt_resample_u8(ptr(pixels), n, hs, ws, ptr(out), ptr(table), capacity, ptr(scratch), scratch.numel() * scratch.element_size(),
-                                stream_ptr()), L)
-    return out
+    return _resample_bicubic("dyt_resample_u8", "device crop / resize", False, pixels, table, draw, out, scratch)
 
 
 def resample_coeffs(table, row, src_h, src_w):
     """dyt_resample_coeffs: the coefficient tables the kernels compute for table row ``row`` of a batch padded to src_h x src_w -> int32
     [2, 13, 224] on the device (axis 0 = output rows, 1 = columns; first tap, tap count, 11 coefficients per window position)."""
-    import torch
-    L = lib()
-    if not hasattr(L, "dyt_resample_coeffs"):
-        raise DyTError("this libdyt_hip has no dyt_resample_coeffs (device crop / resize): rebuild it")
-    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
-    out = torch.zeros(2, 13, 224, device=table.device, dtype=torch.int32)
-    with torch.cuda.device(table.device):
-        check(L.dyt_resample_coeffs(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
-    return out
+    return _resample_coeffs("dyt_resample_coeffs", "device crop / resize", 13, table, row, src_h, src_w)
 
 
 RESAMPLE_WIDE_KMAX, RESAMPLE_WIDE_COEFF_WORDS, RESAMPLE_WIDE_ROW_BYTES = 75, 2 * 77 * 224, 672   # csrc/resample_wide.h
@@ -366,41 +373,13 @@ def resample_wide_u8(pixels, table, draw=None, out=None, scratch=None):
     2.5 times the size it is resized to (up to 75 taps per position; csrc/resample_wide.h).  ``draw``: checked on the host first, as a wide
     draw.  ``scratch``: an int32 device buffer of dyt_resample_wide_scratch_bytes(B, Hs) bytes at least (coefficients and the intermediate
     rows), allocated here when absent."""
-    import torch
-    L = lib()
-    n, hs, ws, capacity = _resample_args(L, pixels, table)
-    if not hasattr(L, "dyt_resample_wide_u8") or not hasattr(L, "dyt_resample_wide_scratch_bytes"):
-        raise DyTError("this libdyt_hip has no dyt_resample_wide_u8 (device crop / resize at any downscale): rebuild it")
-    if draw is not None:
-        if draw.units != n:
-            raise DyTError("resample: the draw holds %d images, the batch %d" % (draw.units, n))
-        try:
-            draw.check(hs, ws, wide=True)
-        except ValueError as e:
-            raise DyTError(str(e))
-    pixels = pixels.contiguous()
-    if out is None:
-        out = torch.empty(n, 224, 224, 3, device=pixels.device, dtype=torch.uint8)
-    if scratch is None:
-        scratch = torch.empty(int(L.dyt_resample_wide_scratch_bytes(n, hs)) // 4, device=pixels.device, dtype=torch.int32)
-    with torch.cuda.device(pixels.device):
-        check(L.dyt_resample_wide_u8(ptr(pixels), n, hs, ws, ptr(out), ptr(table), capacity, ptr(scratch),
-                                     scratch.numel() * scratch.element_size(), stream_ptr()), L)
-    return out
+    return _resample_bicubic("dyt_resample_wide_u8", "device crop / resize at any downscale", True, pixels, table, draw, out, scratch)
 
 
 def resample_wide_coeffs(table, row, src_h, src_w):
     """dyt_resample_wide_coeffs: the coefficient tables the wide kernels compute for table row ``row`` of a batch padded to src_h x src_w
     -> int32 [2, 77, 224] on the device (axis 0 = output rows, 1 = columns; first tap, tap count, 75 coefficients per window position)."""
-    import torch
-    L = lib()
-    if not hasattr(L, "dyt_resample_wide_coeffs"):
-        raise DyTError("this libdyt_hip has no dyt_resample_wide_coeffs (device crop / resize at any downscale): rebuild it")
-    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
-    out = torch.zeros(2, 2 + RESAMPLE_WIDE_KMAX, 224, device=table.device, dtype=torch.int32)
-    with torch.cuda.device(table.device):
-        check(L.dyt_resample_wide_coeffs(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
-    return out
+    return _resample_coeffs("dyt_resample_wide_coeffs", "device crop / resize at any downscale", 2 + RESAMPLE_WIDE_KMAX, table, row, src_h, src_w)
 
 
 RESAMPLE_BILINEAR_F32, RESAMPLE_CLIP_COEFF_WORDS = 2, 2 * 4 * 224   # csrc/resample_clip.h
@@ -453,15 +432,7 @@ def resample_clip_f32(clips, table, draw=None, out=None, norm=None, units=None):
 def resample_clip_coeffs(table, row, src_h, src_w):
     """dyt_resample_clip_coeffs: the taps and weights the kernel computes for clip row ``row`` of a batch padded to src_h x src_w -> int32
     [2, 4, 224] on the device (axis 0 = output rows, 1 = columns; i0, i1 relative to the box, the bit patterns of l0 and l1)."""
-    import torch
-    L = lib()
-    if not hasattr(L, "dyt_resample_clip_coeffs"):
-        raise DyTError("this libdyt_hip has no dyt_resample_clip_coeffs (device clip pipeline): rebuild it")
-    capacity = (int(table.numel()) - RESAMPLE_HEADER_WORDS) // RESAMPLE_ROW_WORDS
-    out = torch.zeros(2, 4, 224, device=table.device, dtype=torch.int32)
-    with torch.cuda.device(table.device):
-        check(L.dyt_resample_clip_coeffs(ptr(table), capacity, int(row), int(src_h), int(src_w), ptr(out), stream_ptr()), L)
-    return out
+    return _resample_coeffs("dyt_resample_clip_coeffs", "device clip pipeline", 4, table, row, src_h, src_w)
 
 
 RANDAUG_HEADER_WORDS, RANDAUG_ROW_WORDS, RANDAUG_HIST_WORDS, RANDAUG_TABLE_WORDS, RANDAUG_MAX_LAYERS = 16, 20, 4 * 256, 3 * 256 + 1, 8   # csrc/randaug.h

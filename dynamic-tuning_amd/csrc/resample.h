@@ -44,15 +44,21 @@ struct ResampleRow {
 };
 static_assert(sizeof(ResampleRow) == RS_ROW_WORDS * 4 && sizeof(ResampleRow) % 16 == 0, "ResampleRow is 12 words: rows stay 16-byte aligned");
 
-// Everything a kernel later indexes with, compared in 64-bit first.  box <= 2.5 * full per axis bounds the taps by RS_KMAX.
-DYT_RESAMPLE_HD inline bool resample_row_ok(const ResampleRow& r, int batch_src_h, int batch_src_w) {
+// Everything a kernel later indexes with, compared in 64-bit first: the one row check of both bicubic routes.  bounded: box <= 2.5 * full
+// per axis, which bounds the taps by RS_KMAX (the 11-tap route).  Not bounded (resample_wide.h): a batch side above RS_MAX_SIDE is refused
+// instead, so that box <= src <= batch <= 4096 and full >= 224 bound the taps by RSW_KMAX.
+DYT_RESAMPLE_HD inline bool resample_row_ok_core(const ResampleRow& r, int batch_src_h, int batch_src_w, bool bounded) {
     const long long sh = r.src_h, sw = r.src_w, t = r.top, l = r.left, bh = r.box_h, bw = r.box_w;
     const long long fh = r.full_h, fw = r.full_w, oy = r.off_y, ox = r.off_x;
+    if (!bounded && (batch_src_h > RS_MAX_SIDE || batch_src_w > RS_MAX_SIDE)) return false;
     if (sh < 1 || sw < 1 || sh > batch_src_h || sw > batch_src_w) return false;
     if (bh < 1 || bw < 1 || t < 0 || l < 0 || t + bh > sh || l + bw > sw) return false;
     if (fh < RS_OUT || fw < RS_OUT || oy < 0 || ox < 0 || oy + RS_OUT > fh || ox + RS_OUT > fw) return false;
-    if (2 * bh > 5 * fh || 2 * bw > 5 * fw) return false;
+    if (bounded && (2 * bh > 5 * fh || 2 * bw > 5 * fw)) return false;
     return true;
+}
+DYT_RESAMPLE_HD inline bool resample_row_ok(const ResampleRow& r, int batch_src_h, int batch_src_w) {
+    return resample_row_ok_core(r, batch_src_h, batch_src_w, true);
 }
 
 // The row of image n, chosen from the image number alone; -1: no row
@@ -69,10 +75,13 @@ DYT_RESAMPLE_HD inline double resample_bicubic(double x) {
     return 0.0;
 }
 
-// Output position xx of an axis that resizes `in` source pixels to `out`: the first tap, the tap count (<= RS_KMAX for in <= 2.5 out) and
-// the 22-bit coefficients; k[count..RS_KMAX) = 0.  All of it in fp64 without contraction: a fused multiply-add rounds once where Pillow's
-// x86-64 build rounds twice, and the integers would differ.
-DYT_RESAMPLE_HD inline void resample_coeffs(int in, int out, int xx, int& xmin, int& count, int (&k)[RS_KMAX]) {
+// Output position xx of an axis that resizes `in` source pixels to `out`: the first tap, the tap count (<= KMAX: RS_KMAX for in <= 2.5 out,
+// resample_wide.h's RSW_KMAX for in <= 4096 and out >= 224) and the 22-bit coefficients; k[count..KMAX) = 0.  One definition for every tap
+// bound, so xmin, count and the first integers of a wider instantiation are a narrower one's.  All of it in fp64 without contraction: a
+// fused multiply-add rounds once where Pillow's x86-64 build rounds twice, and the integers would differ.  The weights are formed twice
+// (once for their sum, in index order, once to be normalised) instead of being kept: a device thread then needs no array of KMAX doubles.
+template <int KMAX>
+DYT_RESAMPLE_HD inline void resample_coeffs_taps(int in, int out, int xx, int& xmin, int& count, int (&k)[KMAX]) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -87,23 +96,22 @@ DYT_RESAMPLE_HD inline void resample_coeffs(int in, int out, int xx, int& xmin, 
     if (hi > in) hi = in;
     int n = hi - lo;
     if (n < 0) n = 0;
-    if (n > RS_KMAX) n = RS_KMAX;
-    double w[RS_KMAX];
+    if (n > KMAX) n = KMAX;
     double ww = 0.0;
-    for (int x = 0; x < RS_KMAX; ++x) {
-        w[x] = 0.0;
+    for (int x = 0; x < n; ++x) ww += resample_bicubic((x + lo - center + 0.5) * ss);
+    for (int x = 0; x < KMAX; ++x) {
+        double v = 0.0;
         if (x < n) {
-            w[x] = resample_bicubic((x + lo - center + 0.5) * ss);
-            ww += w[x];
+            v = resample_bicubic((x + lo - center + 0.5) * ss);
+            if (ww != 0.0) v = v / ww;
         }
-    }
-    for (int x = 0; x < RS_KMAX; ++x) {
-        double v = w[x];
-        if (x < n && ww != 0.0) v = v / ww;
         k[x] = v < 0 ? (int)(-0.5 + v * (double)(1 << RS_PRECISION_BITS)) : (int)(0.5 + v * (double)(1 << RS_PRECISION_BITS));
     }
     xmin = lo;
     count = n;
+}
+DYT_RESAMPLE_HD inline void resample_coeffs(int in, int out, int xx, int& xmin, int& count, int (&k)[RS_KMAX]) {
+    resample_coeffs_taps<RS_KMAX>(in, out, xx, xmin, count, k);
 }
 
 // Pillow's clip8 of an accumulator that started at 2^21

@@ -1,5 +1,6 @@
 // Device clip pipeline from byte clips: two context-free entries (dyt_resample_clip_f32, dyt_resample_clip_coeffs).  The row check, the
-// index / weight function, the two-tap arithmetic and every argument check are resample_clip.h; the table layout is resample.h's.
+// index / weight function, the two-tap arithmetic and every argument check are resample_clip.h; the table layout is resample.h's; the
+// row loader and the staging of a source row segment into LDS are resample_dev.h's, shared with the bicubic routes.
 //
 //   resample_clip_kernel         one block per (band of 8 output rows, frame, unit).  The block builds the 3 x 256 table of
 //                                input_norm_value in LDS (as the byte loaders do), reads ITS row of the table -- one row serves all
@@ -15,9 +16,8 @@
 // Nothing read from the table is used as an index before clip_row_ok has compared it (64-bit) against the batch's shape; a unit whose
 // row fails the check, or that has no row, is written as zeros.  A 16-byte load is issued only where all 16 bytes lie inside the source
 // allocation; the chunk that would cross its end is read byte by byte.  One writer per value, no atomics.  The same code in both builds.
-#include "../../include/dyt_hip.h"
-#include "dyt_common.h"
 #include "input_u8_dev.h"
+#include "resample_dev.h"
 #include "resample_clip.h"
 
 namespace dyt {
@@ -29,17 +29,8 @@ constexpr int RC_STAGE = RS_MAX_SIDE * 3 + 32;               // bytes of one sta
 static_assert(RS_OUT % RC_BAND == 0 && RC_STAGE % 16 == 0, "bands tile the window; staged rows stay 16-byte aligned");
 
 // false: unit u has no valid row (filter, units, capacity, clip_row_ok) and is written as zeros
-__device__ __forceinline__ bool clip_load_row(const int* __restrict__ table, int u, int capacity, int batch, int Hs, int Ws, ResampleRow& r) {
-    const int2 h = *reinterpret_cast<const int2*>(table);
-    if (h.x != RS_BILINEAR_F32) return false;
-    const int k = resample_unit(u, h.y, capacity);
-    if (k < 0) return false;
-    const int4* q = reinterpret_cast<const int4*>(table + RS_HEADER_WORDS + (size_t)k * RS_ROW_WORDS);
-    const int4 q0 = q[0], q1 = q[1], q2 = q[2];
-    r.src_h = q0.x; r.src_w = q0.y; r.top = q0.z; r.left = q0.w;
-    r.box_h = q1.x; r.box_w = q1.y; r.full_h = q1.z; r.full_w = q1.w;
-    r.off_y = q2.x; r.off_x = q2.y; r.flags = q2.z; r.pad = q2.w;
-    return clip_row_ok(r, batch, Hs, Ws);
+__device__ __forceinline__ bool load_row(const int* __restrict__ table, int u, int capacity, int batch, int Hs, int Ws, ResampleRow& r) {
+    return resample_load_row(table, RS_BILINEAR_F32, u, capacity, r) && clip_row_ok(r, batch, Hs, Ws);
 }
 
 }  // namespace
@@ -51,7 +42,7 @@ __global__ __launch_bounds__(256) void resample_clip_kernel(const uint8_t* __res
     const int tid = threadIdx.x, oy0 = blockIdx.x * RC_BAND, f = blockIdx.y, u = blockIdx.z;
     float* out = dst + ((size_t)u * frames + f) * 3 * RS_OUT * RS_OUT;
     ResampleRow row;
-    if (!clip_load_row(table, u, capacity, batch, Hs, Ws, row)) {   // uniform over the block
+    if (!load_row(table, u, capacity, batch, Hs, Ws, row)) {   // uniform over the block
         for (int i = tid; i < 3 * RC_BAND * RS_OUT / 4; i += 256) {
             const int c = i / (RC_BAND * RS_OUT / 4), j = i - c * (RC_BAND * RS_OUT / 4);
             reinterpret_cast<float4*>(out + (size_t)c * RS_OUT * RS_OUT + oy0 * RS_OUT)[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -87,26 +78,8 @@ __global__ __launch_bounds__(256) void resample_clip_kernel(const uint8_t* __res
         clip_axis(row.box_h, row.full_h, row.off_y + oy, y[0], y[1], ly0, ly1);
         int shift[2];
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const long long lo = ((plane + row.top + y[s]) * Ws + row.left + xs_lo) * 3;   // first byte of the span, from src
-            const long long a0 = lo & ~15LL;
-            shift[s] = (int)(lo - a0);
-            int chunks = (shift[s] + span + 15) >> 4;
-            if (chunks > RC_STAGE / 16) chunks = RC_STAGE / 16;
-            for (int q = tid; q < chunks; q += 256) {
-                const long long at = a0 + 16LL * q;
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (at + 16 <= total) {
-                    v = *reinterpret_cast<const uint4*>(src + at);
-                } else {   // the chunk that would cross the end of the allocation
-                    unsigned w[4] = {0u, 0u, 0u, 0u};
-                    for (int e = 0; e < 16; ++e)
-                        if (at + e < total) w[e >> 2] |= (unsigned)src[at + e] << (8 * (e & 3));
-                    v = make_uint4(w[0], w[1], w[2], w[3]);
-                }
-                *reinterpret_cast<uint4*>(&stage[s][16 * q]) = v;
-            }
-        }
+        for (int s = 0; s < 2; ++s)   // the span's bytes of source rows y[0], y[1]
+            shift[s] = resample_stage_row(src, total, ((plane + row.top + y[s]) * Ws + row.left + xs_lo) * 3, span, stage[s], RC_STAGE / 16, tid);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -128,7 +101,7 @@ __global__ __launch_bounds__(256) void resample_clip_coeff_kernel(const int* __r
     const int axis = blockIdx.x, t = threadIdx.x;
     if (t >= RS_OUT) return;
     ResampleRow r;
-    const bool ok = clip_load_row(table, unit, capacity, 0x7FFFFFFF, Hs, Ws, r);   // (no source is read here: any src >= 0 passes)
+    const bool ok = load_row(table, unit, capacity, 0x7FFFFFFF, Hs, Ws, r);   // (no source is read here: any src >= 0 passes)
     int i0 = 0, i1 = 0;
     float l0 = 0.0f, l1 = 0.0f;
     if (ok) {
@@ -146,11 +119,9 @@ __global__ __launch_bounds__(256) void resample_clip_coeff_kernel(const int* __r
 
 using namespace dyt;
 
-static unsigned long long rc_addr(const void* p) { return (unsigned long long)reinterpret_cast<uintptr_t>(p); }
-
 extern "C" int dyt_resample_clip_f32(const uint8_t* src, int batch, int frames, int src_h, int src_w, float* dst, int units,
                                      const void* table_dev, int capacity, const float mean[3], const float std[3], void* stream) {
-    if (const char* e = clip_ptr_error(rc_addr(src), rc_addr(dst), rc_addr(table_dev))) { set_error("dyt_resample_clip_f32: %s", e); return DYT_ERR_ARG; }
+    if (const char* e = clip_ptr_error(resample_addr(src), resample_addr(dst), resample_addr(table_dev))) { set_error("dyt_resample_clip_f32: %s", e); return DYT_ERR_ARG; }
     if (const char* e = clip_shape_error(batch, frames, src_h, src_w, units, capacity)) {
         set_error("dyt_resample_clip_f32: %s (batch %d, frames %d, source %d x %d, units %d, table capacity %d)", e, batch, frames, src_h, src_w,
                   units, capacity);
@@ -166,9 +137,8 @@ extern "C" int dyt_resample_clip_f32(const uint8_t* src, int batch, int frames, 
 }
 
 extern "C" int dyt_resample_clip_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream) {
-    if (const char* e = clip_ptr_error(16, rc_addr(out_dev), rc_addr(table_dev))) { set_error("dyt_resample_clip_coeffs: %s", e); return DYT_ERR_ARG; }
-    if (const char* e = clip_shape_error(1, 1, src_h, src_w, 1, capacity)) { set_error("dyt_resample_clip_coeffs: %s", e); return DYT_ERR_ARG; }
-    if (row < 0 || row >= capacity) { set_error("dyt_resample_clip_coeffs: row %d is outside the table's %d rows", row, capacity); return DYT_ERR_ARG; }
+    if (resample_coeffs_refusal("dyt_resample_clip_coeffs", clip_ptr_error(16, resample_addr(out_dev), resample_addr(table_dev)),
+                                clip_shape_error(1, 1, src_h, src_w, 1, capacity), row, capacity)) return DYT_ERR_ARG;
     hipLaunchKernelGGL(resample_clip_coeff_kernel, dim3(2, 1), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const int*>(table_dev), capacity, src_h, src_w, row, out_dev);
     DYT_HIP_CHECK(hipGetLastError());

@@ -1,9 +1,10 @@
 // Device crop / resize at any downscale: three context-free entries (dyt_resample_wide_u8, dyt_resample_wide_scratch_bytes,
-// dyt_resample_wide_coeffs) beside the 11-tap route of resample.hip, which this file does not touch.  The table layout and the filter are
-// resample.h; the row check without the 2.5 bound, the 75-tap coefficient function and every argument check are resample_wide.h.
+// dyt_resample_wide_coeffs) beside the 11-tap route of resample.hip.  The table layout, the filter and the coefficient template are
+// resample.h; the row check without the 2.5 bound, the tap bound and every argument check are resample_wide.h; the device pieces shared
+// with the other two routes (row loader, tap range, staging, accumulate and guarded pack, zero fill, the coefficient kernel) are
+// resample_dev.h.
 //
-//   resample_wide_coeff_kernel   one block per (axis, image): thread t computes resample_wide_coeffs of window position t -- first tap,
-//                                tap count, 75 coefficients, fp64 without contraction -- into the scratch buffer, [axis][field][224] ints
+//   resample_coeff_kernel<75>    resample_dev.h's: first tap, tap count and 75 coefficients per window position into the scratch buffer
 //   resample_wide_h_kernel       one block per (4 source rows, image): the box segment of each row that the window's vertical taps need is
 //                                staged in LDS with aligned 16-byte loads; work item ox forms output pixel ox of all 4 rows, reading each
 //                                coefficient once, and stores the bytes (mirrored if asked) to tmp[image][source row][672] in scratch
@@ -18,8 +19,7 @@
 // compared it (64-bit) against the batch's shape; the coefficient bounds read back from scratch are clamped against the box again.  An
 // image whose row fails the check is written as zeros.  One writer per byte, no atomics, no floating point in the pixel passes.  The
 // 16-byte loads that stage a row may take in bytes beside the box (never beyond the source allocation); no output depends on them.
-#include "../../include/dyt_hip.h"
-#include "dyt_common.h"
+#include "resample_dev.h"
 #include "resample_wide.h"
 
 namespace dyt {
@@ -27,59 +27,18 @@ namespace dyt {
 namespace {
 
 constexpr int RSW_HROWS = 4;                // source rows per block of the horizontal pass
-constexpr int RSW_BAND = 16;                // output rows per block of the vertical pass
-constexpr int RSW_GROUPS = RSW_ROW_BYTES / 16;
+static_assert(RSW_ROW_BYTES == RS_ROWB, "a row of tmp is a 224-pixel byte row");
 constexpr int RSW_FIELD_WORDS = RSW_COEFF_FIELDS * RS_OUT;   // one axis of one image
 
 // bytes of LDS one staged row takes: the widest box segment, the bytes in front of it down to a 16-byte boundary and behind it up to one
 __host__ __device__ inline int rsw_lds_stride(int Ws) { return ((Ws * 3 + 15) & ~15) + 32; }
 
 // false: image b has no valid row (filter, units, capacity, resample_wide_row_ok) and is written as zeros
-__device__ __forceinline__ bool rsw_load_row(const int* __restrict__ table, int b, int capacity, int Hs, int Ws, ResampleRow& r) {
-    const int2 h = *reinterpret_cast<const int2*>(table);
-    if (h.x != RS_BICUBIC) return false;
-    const int u = resample_unit(b, h.y, capacity);
-    if (u < 0) return false;
-    const int4* q = reinterpret_cast<const int4*>(table + RS_HEADER_WORDS + (size_t)u * RS_ROW_WORDS);
-    const int4 q0 = q[0], q1 = q[1], q2 = q[2];
-    r.src_h = q0.x; r.src_w = q0.y; r.top = q0.z; r.left = q0.w;
-    r.box_h = q1.x; r.box_w = q1.y; r.full_h = q1.z; r.full_w = q1.w;
-    r.off_y = q2.x; r.off_x = q2.y; r.flags = q2.z; r.pad = 0;
-    return resample_wide_row_ok(r, Hs, Ws);
-}
-
-__device__ __forceinline__ int rsw_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// resample_clip8 as an opaque 32-bit value.  Left to itself hipcc fuses two neighbouring shift-and-clamps of a packed word into
-// v_ashr_pk_u8_i32 and then takes the upper half of that instruction's destination for zero; the instruction leaves it as it was, and the
-// stray bits are ORed into bytes 2 and 3 of the word (seen on the MI355X: those bytes came out as supersets of the right bits).  The empty
-// asm statement keeps each byte a value of its own, so the word is built from four clamps, three shifts and an OR.
-__device__ __forceinline__ unsigned rsw_byte(int ss) {
-    unsigned v = (unsigned)resample_clip8(ss);
-    asm("" : "+v"(v));
-    return v;
+__device__ __forceinline__ bool load_row(const int* __restrict__ table, int b, int capacity, int Hs, int Ws, ResampleRow& r) {
+    return resample_load_row(table, RS_BICUBIC, b, capacity, r) && resample_wide_row_ok(r, Hs, Ws);
 }
 
 }  // namespace
-
-__global__ __launch_bounds__(256) void resample_wide_coeff_kernel(const int* __restrict__ table, int capacity, int Hs, int Ws, int img_base,
-                                                                  int* __restrict__ out) {
-    const int axis = blockIdx.x, t = threadIdx.x;
-    if (t >= RS_OUT) return;
-    ResampleRow r;
-    const bool ok = rsw_load_row(table, img_base + (int)blockIdx.y, capacity, Hs, Ws, r);
-    int xmin = 0, count = 0;
-    int k[RSW_KMAX];
-    for (int x = 0; x < RSW_KMAX; ++x) k[x] = 0;
-    if (ok) {
-        if (axis == 0) resample_wide_coeffs(r.box_h, r.full_h, r.off_y + t, xmin, count, k);
-        else resample_wide_coeffs(r.box_w, r.full_w, r.off_x + t, xmin, count, k);
-    }
-    int* o = out + (size_t)blockIdx.y * RSW_COEFF_WORDS + axis * RSW_FIELD_WORDS + t;
-    o[0] = xmin;
-    o[RS_OUT] = count;
-    for (int x = 0; x < RSW_KMAX; ++x) o[(2 + x) * RS_OUT] = k[x];
-}
 
 // grid (ceil(Hs / RSW_HROWS), B), 256 work items, rsw_lds_stride(Ws) * RSW_HROWS bytes of dynamic LDS
 __global__ __launch_bounds__(256) void resample_wide_h_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, long long src_bytes,
@@ -88,45 +47,32 @@ __global__ __launch_bounds__(256) void resample_wide_h_kernel(const uint8_t* __r
     extern __shared__ __attribute__((aligned(16))) uint8_t seg[];   // [RSW_HROWS][stride]: the rows' box segments from a 16-byte boundary on
     const int b = blockIdx.y, tid = threadIdx.x;
     ResampleRow row;
-    if (!rsw_load_row(table, b, capacity, Hs, Ws, row)) return;     // uniform over the block; the vertical pass writes the zeros
+    if (!load_row(table, b, capacity, Hs, Ws, row)) return;     // uniform over the block; the vertical pass writes the zeros
     const int* vc = coeffs + (size_t)b * RSW_COEFF_WORDS;
     const int* hc = vc + RSW_FIELD_WORDS;
     // the source rows (relative to the box) the window's vertical taps read: the first position's first tap to the last position's last
     // (both bounds grow with the position).  Bounds from scratch are clamped against the box again.
-    const int lo_a = rsw_clamp(vc[0], 0, row.box_h - 1);
-    const int lo_z = rsw_clamp(vc[RS_OUT - 1], 0, row.box_h - 1);
-    const int n_z = rsw_clamp(vc[RS_OUT + RS_OUT - 1], 0, min(RSW_KMAX, row.box_h - lo_z));
+    const int lo_a = resample_clampi(vc[0], 0, row.box_h - 1);
+    int lo_z, n_z;
+    resample_tap_range<RSW_KMAX>(vc[RS_OUT - 1], vc[RS_OUT + RS_OUT - 1], row.box_h, lo_z, n_z);
     const int y0 = max(row.top + lo_a, (int)blockIdx.x * RSW_HROWS);                    // absolute source rows [y0, y1) of this block
     const int y1 = min(row.top + lo_z + n_z, (int)blockIdx.x * RSW_HROWS + RSW_HROWS);
     const int nr = y1 - y0;
     if (nr <= 0) return;                                                                // rows outside the box or the needed range
     const int stride = rsw_lds_stride(Ws);
-    const int seg_bytes = row.box_w * 3;
     int head[RSW_HROWS];                                                                // bytes in front of the segment in the row's LDS
 #pragma unroll
     for (int r = 0; r < RSW_HROWS; ++r) {
         head[r] = 0;
-        if (r < nr) {
-            const long long first = (((long long)b * Hs + y0 + r) * Ws + row.left) * 3;    // < src_bytes: the box lies inside the batch
-            const long long from = first & ~15LL;
-            head[r] = (int)(first - from);
-            const int runs = (head[r] + seg_bytes + 15) >> 4;                           // <= stride / 16
-            uint8_t* d = seg + r * stride;
-            for (int i = tid; i < runs; i += 256) {
-                const long long at = from + 16LL * i;
-                if (at + 16 <= src_bytes) {
-                    *reinterpret_cast<uint4*>(d + 16 * i) = *reinterpret_cast<const uint4*>(src + at);
-                } else {                                                                // the last run of the allocation: byte by byte
-                    for (int j = 0; j < 16; ++j) d[16 * i + j] = at + j < src_bytes ? src[at + j] : (uint8_t)0;
-                }
-            }
-        }
+        if (r < nr)                                                                     // (first < src_bytes: the box lies inside the batch)
+            head[r] = resample_stage_row(src, src_bytes, (((long long)b * Hs + y0 + r) * Ws + row.left) * 3, row.box_w * 3, seg + r * stride,
+                                         stride / 16, tid);
     }
     __syncthreads();
     if (tid >= RS_OUT) return;
     const int ox = tid;
-    const int lo = rsw_clamp(hc[ox], 0, row.box_w - 1);
-    const int n = rsw_clamp(hc[RS_OUT + ox], 0, min(RSW_KMAX, row.box_w - lo));
+    int lo, n;
+    resample_tap_range<RSW_KMAX>(hc[ox], hc[RS_OUT + ox], row.box_w, lo, n);
     int acc[RSW_HROWS][3];
     const uint8_t* p[RSW_HROWS];
 #pragma unroll
@@ -157,44 +103,32 @@ __global__ __launch_bounds__(256) void resample_wide_h_kernel(const uint8_t* __r
     }
 }
 
-// grid (224 / RSW_BAND, B), 256 work items
+// grid (224 / RS_BAND, B), 256 work items
 __global__ __launch_bounds__(256) void resample_wide_v_kernel(int Hs, int Ws, uint8_t* __restrict__ dst, const int* __restrict__ table,
                                                               int capacity, const int* __restrict__ coeffs, const uint8_t* __restrict__ tmp) {
-    __shared__ int vc[RSW_COEFF_FIELDS * RSW_BAND];   // row coefficients of this band [field][16]
-    const int b = blockIdx.y, oy0 = blockIdx.x * RSW_BAND, tid = threadIdx.x;
+    __shared__ int vc[RSW_COEFF_FIELDS * RS_BAND];   // row coefficients of this band [field][16]
+    const int b = blockIdx.y, oy0 = blockIdx.x * RS_BAND, tid = threadIdx.x;
     uint8_t* out = dst + ((size_t)b * RS_OUT + oy0) * RSW_ROW_BYTES;
     ResampleRow row;
-    if (!rsw_load_row(table, b, capacity, Hs, Ws, row)) {   // uniform over the block
-        for (int i = tid; i < RSW_BAND * RSW_GROUPS; i += 256) reinterpret_cast<uint4*>(out)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (!load_row(table, b, capacity, Hs, Ws, row)) {   // uniform over the block
+        resample_zero_band(out, tid);
         return;
     }
     const int* cf = coeffs + (size_t)b * RSW_COEFF_WORDS;
-    for (int i = tid; i < RSW_COEFF_FIELDS * RSW_BAND; i += 256) {
-        const int f = i / RSW_BAND, j = i - f * RSW_BAND;
+    for (int i = tid; i < RSW_COEFF_FIELDS * RS_BAND; i += 256) {
+        const int f = i / RS_BAND, j = i - f * RS_BAND;
         vc[i] = cf[f * RS_OUT + oy0 + j];
     }
     __syncthreads();
     const uint8_t* rows = tmp + ((size_t)b * Hs + row.top) * RSW_ROW_BYTES;   // the box's first row
-    for (int idx = tid; idx < RSW_BAND * RSW_GROUPS; idx += 256) {
-        const int j = idx / RSW_GROUPS, g = idx - j * RSW_GROUPS;
-        const int lo = rsw_clamp(vc[j], 0, row.box_h - 1);
-        const int n = rsw_clamp(vc[RSW_BAND + j], 0, min(RSW_KMAX, row.box_h - lo));
-        int acc[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 1 << (RS_PRECISION_BITS - 1);
+    for (int idx = tid; idx < RS_BAND * RS_GROUPS; idx += 256) {
+        const int j = idx / RS_GROUPS, g = idx - j * RS_GROUPS;
+        int lo, n, acc[16];
+        resample_tap_range<RSW_KMAX>(vc[j], vc[RS_BAND + j], row.box_h, lo, n);
+        resample_acc_start(acc);
         const uint8_t* p = rows + (size_t)lo * RSW_ROW_BYTES + g * 16;
-        for (int x = 0; x < n; ++x) {
-            const int k = vc[(2 + x) * RSW_BAND + j];
-            const uint4 v = *reinterpret_cast<const uint4*>(p + (size_t)x * RSW_ROW_BYTES);
-            const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] += (int)((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) * k;
-        }
-        unsigned w[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-            w[d] = rsw_byte(acc[4 * d]) | (rsw_byte(acc[4 * d + 1]) << 8) | (rsw_byte(acc[4 * d + 2]) << 16) | (rsw_byte(acc[4 * d + 3]) << 24);
-        *reinterpret_cast<uint4*>(out + j * RSW_ROW_BYTES + g * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        for (int x = 0; x < n; ++x) resample_acc_add(acc, *reinterpret_cast<const uint4*>(p + (size_t)x * RSW_ROW_BYTES), vc[(2 + x) * RS_BAND + j]);
+        *reinterpret_cast<uint4*>(out + j * RSW_ROW_BYTES + g * 16) = resample_acc_pack(acc);
     }
 }
 
@@ -202,13 +136,11 @@ __global__ __launch_bounds__(256) void resample_wide_v_kernel(int Hs, int Ws, ui
 
 using namespace dyt;
 
-static unsigned long long rsw_addr(const void* p) { return (unsigned long long)reinterpret_cast<uintptr_t>(p); }
-
 extern "C" int64_t dyt_resample_wide_scratch_bytes(int batch, int src_h) { return resample_wide_scratch_bytes(batch, src_h); }
 
 extern "C" int dyt_resample_wide_u8(const uint8_t* src, int batch, int src_h, int src_w, uint8_t* dst, const void* table_dev, int capacity,
                                     void* scratch_dev, int64_t scratch_bytes, void* stream) {
-    if (const char* e = resample_wide_args_error(rsw_addr(src), rsw_addr(dst), rsw_addr(table_dev), rsw_addr(scratch_dev), batch, src_h, src_w,
+    if (const char* e = resample_wide_args_error(resample_addr(src), resample_addr(dst), resample_addr(table_dev), resample_addr(scratch_dev), batch, src_h, src_w,
                                                  capacity, scratch_bytes)) {
         set_error("dyt_resample_wide_u8: %s (batch %d, source %d x %d, table capacity %d, %lld scratch bytes given, %lld needed)", e, batch,
                   src_h, src_w, capacity, (long long)scratch_bytes, resample_wide_scratch_bytes(batch, src_h));
@@ -219,22 +151,21 @@ extern "C" int dyt_resample_wide_u8(const uint8_t* src, int batch, int src_h, in
     int* coeffs = static_cast<int*>(scratch_dev);
     uint8_t* tmp = static_cast<uint8_t*>(scratch_dev) + resample_wide_coeff_bytes(batch);
     const long long src_bytes = (long long)batch * src_h * src_w * 3;
-    hipLaunchKernelGGL(resample_wide_coeff_kernel, dim3(2, (unsigned)batch), dim3(256), 0, s, table, capacity, src_h, src_w, 0, coeffs);
+    hipLaunchKernelGGL(resample_coeff_kernel<RSW_KMAX>, dim3(2, (unsigned)batch), dim3(256), 0, s, table, capacity, src_h, src_w, 0, coeffs);
     DYT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(resample_wide_h_kernel, dim3((unsigned)((src_h + RSW_HROWS - 1) / RSW_HROWS), (unsigned)batch), dim3(256),
                        (size_t)rsw_lds_stride(src_w) * RSW_HROWS, s, src, src_h, src_w, src_bytes, table, capacity, (const int*)coeffs, tmp);
     DYT_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(resample_wide_v_kernel, dim3(RS_OUT / RSW_BAND, (unsigned)batch), dim3(256), 0, s, src_h, src_w, dst, table, capacity,
+    hipLaunchKernelGGL(resample_wide_v_kernel, dim3(RS_OUT / RS_BAND, (unsigned)batch), dim3(256), 0, s, src_h, src_w, dst, table, capacity,
                        (const int*)coeffs, (const uint8_t*)tmp);
     DYT_HIP_CHECK(hipGetLastError());
     return DYT_OK;
 }
 
 extern "C" int dyt_resample_wide_coeffs(const void* table_dev, int capacity, int row, int src_h, int src_w, int32_t* out_dev, void* stream) {
-    if (const char* e = resample_ptr_error(16, rsw_addr(out_dev), rsw_addr(table_dev), 16)) { set_error("dyt_resample_wide_coeffs: %s", e); return DYT_ERR_ARG; }
-    if (const char* e = resample_shape_error(1, src_h, src_w, capacity)) { set_error("dyt_resample_wide_coeffs: %s", e); return DYT_ERR_ARG; }
-    if (row < 0 || row >= capacity) { set_error("dyt_resample_wide_coeffs: row %d is outside the table's %d rows", row, capacity); return DYT_ERR_ARG; }
-    hipLaunchKernelGGL(resample_wide_coeff_kernel, dim3(2, 1), dim3(256), 0, static_cast<hipStream_t>(stream),
+    if (resample_coeffs_refusal("dyt_resample_wide_coeffs", resample_ptr_error(16, resample_addr(out_dev), resample_addr(table_dev), 16),
+                                resample_shape_error(1, src_h, src_w, capacity), row, capacity)) return DYT_ERR_ARG;
+    hipLaunchKernelGGL(resample_coeff_kernel<RSW_KMAX>, dim3(2, 1), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const int*>(table_dev), capacity, src_h, src_w, row, out_dev);
     DYT_HIP_CHECK(hipGetLastError());
     return DYT_OK;

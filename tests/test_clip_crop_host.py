@@ -47,7 +47,17 @@ def test_header_declares_the_entries_and_no_new_flag():
     assert len(values) == len(set(values)) == 11
 
 
-def test_binding_equals_the_header_and_the_version_stays_5():
+def _refuses_without(monkeypatch, _lib, symbol, call):
+    """``call`` raises a DyTError naming ``symbol`` and "rebuild it" when the loaded library is one that lacks ``symbol``."""
+    real = _lib.lib()
+    stand_in = types.SimpleNamespace(**{n: getattr(real, n) for n in _lib.SYMBOLS if n != symbol and hasattr(real, n)})
+    monkeypatch.setattr(_lib, "lib", lambda fp16=False: stand_in)
+    with pytest.raises(_lib.DyTError) as e:
+        call()
+    assert symbol in str(e.value) and "rebuild it" in str(e.value), str(e.value)
+
+
+def test_binding_equals_the_header_and_the_version_stays_5(monkeypatch):
     import _lib
     declared = set(re.findall(r"\b(dyt_[a-z0-9_]+)\s*\(", _header()))
     assert ENTRIES <= declared and declared == set(_lib.SYMBOLS)
@@ -57,9 +67,11 @@ def test_binding_equals_the_header_and_the_version_stays_5():
         L = _lib.lib(fp16=fp16)
         assert L.dyt_version() == 5 and all(hasattr(L, n) for n in ENTRIES)
     import runtime
-    for fn in (_lib.resample_clip_f32, _lib.resample_clip_coeffs, runtime.DyTEngine.resample_clip):
+    for fn in (_lib.resample_clip_f32, runtime.DyTEngine.resample_clip):
         src = inspect.getsource(fn)
         assert "hasattr(" in src and "rebuild it" in src
+    # resample_clip_coeffs delegates: called with a library that lacks the symbol, before any argument is looked at
+    _refuses_without(monkeypatch, _lib, "dyt_resample_clip_coeffs", lambda: _lib.resample_clip_coeffs(None, 0, 64, 64))
 
 
 def test_resample_clip_h_is_hip_free_and_one_definition():
@@ -80,9 +92,13 @@ def test_resample_clip_h_is_hip_free_and_one_definition():
     assert int(consts["RS_BILINEAR_F32"]) == crop.BILINEAR_F32 == _lib.RESAMPLE_BILINEAR_F32 == 2
     assert consts["RS_CLIP_MAX_FULL"].replace(" ", "") == "1<<23" and crop.MAX_FULL == 1 << 23
     assert _lib.RESAMPLE_CLIP_COEFF_WORDS == 2 * 4 * 224
-    # resample.h is untouched: the bicubic kernels never read word 11
-    rs = open(os.path.join(CSRC, "resample.hip")).read()
-    assert "r.pad = 0;" in rs and "q2.w" not in rs
+    # the bicubic kernels never read word 11: the shared loader fills it, and neither their files nor their row check name it
+    for name in ("resample.hip", "resample_wide.hip", "resample_wide.h"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert ".pad" not in text and "q2.w" not in text and "clip_row_src" not in text, name
+    rs = open(os.path.join(CSRC, "resample.h")).read()
+    assert ".pad" not in rs.split("resample_row_ok_core(", 1)[1] and "int pad;" in rs
+    assert "r.pad = q2.w;" in open(os.path.join(CSRC, "resample_dev.h")).read()
 
 
 # ---- the entries refuse without a device -------------------------------------------------------------------------------------------------

@@ -61,12 +61,24 @@ def test_binding_equals_the_header_and_the_version_stays_5():
         assert L.dyt_resample_scratch_bytes(0) == 0 and L.dyt_resample_scratch_bytes(-3) == 0
 
 
-def test_python_refuses_by_name_when_the_library_lacks_the_entries():
+def _refuses_without(monkeypatch, _lib, symbol, call):
+    """``call`` raises a DyTError naming ``symbol`` and "rebuild it" when the loaded library is one that lacks ``symbol``."""
+    real = _lib.lib()
+    stand_in = types.SimpleNamespace(**{n: getattr(real, n) for n in _lib.SYMBOLS if n != symbol and hasattr(real, n)})
+    monkeypatch.setattr(_lib, "lib", lambda fp16=False: stand_in)
+    with pytest.raises(_lib.DyTError) as e:
+        call()
+    assert symbol in str(e.value) and "rebuild it" in str(e.value), str(e.value)
+
+
+def test_python_refuses_by_name_when_the_library_lacks_the_entries(monkeypatch):
     import _lib
     import runtime
-    for fn in (_lib._resample_args, _lib.resample_coeffs, runtime.DyTEngine.resample):
-        src = inspect.getsource(fn)
-        assert "hasattr(" in src and "rebuild it" in src
+    src = inspect.getsource(runtime.DyTEngine.resample)
+    assert "hasattr(" in src and "rebuild it" in src
+    # the wrappers delegate to one body: called with a library that lacks the symbol, before any argument is looked at
+    _refuses_without(monkeypatch, _lib, "dyt_resample_u8", lambda: _lib.resample_u8(None, None))
+    _refuses_without(monkeypatch, _lib, "dyt_resample_coeffs", lambda: _lib.resample_coeffs(None, 0, 64, 64))
 
 
 def test_resample_h_is_hip_free_and_fixes_the_strides():

@@ -141,6 +141,18 @@ def test_clip_bits_equal_the_restatement_with_and_without_the_mirror(data, name)
         assert np.array_equal(data.want[name][0], np.stack([tab[c][box[..., c]] for c in range(3)], axis=1))
 
 
+def test_a_clip_that_ends_off_a_16_byte_chunk_is_staged_byte_by_byte_at_its_end():
+    """One frame of 5 x 7 pixels is 105 bytes: the last source row's span ends at the allocation's last byte, so its second 16-byte chunk
+    crosses the end and is filled byte by byte (every other source here is a whole number of chunks)."""
+    src = np.random.default_rng(SEED + 5).integers(0, 256, (1, 1, 5, 7, 3), dtype=np.uint8)
+    rows = [(5, 7, 0, 0, 5, 7) + W + (0, 0)]
+    _draw(rows).check(5, 7, 1)      # legal for this route
+    assert src.nbytes == 105 and src.nbytes % 16 != 0 and (4 * 7 * 3) // 16 * 16 + 32 > src.nbytes
+    want = R.resample_batch(src, rows)
+    _same_bits(_resample(src, rows), want, "5 x 7")
+    _same_bits(_resample(src, _mirrored(rows)), want[..., ::-1].copy(), "5 x 7, mirrored")
+
+
 def test_another_norm_and_both_frames_of_a_clip_come_from_one_row(data):
     norm = ((0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711))
     rows = [SMALL[6], SMALL[7], SMALL[3]]

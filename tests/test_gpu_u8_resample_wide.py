@@ -122,6 +122,17 @@ def test_output_bytes_equal_the_restatement_with_and_without_the_mirror(data, na
     _same_bytes(_resample(data.src[name], mixed), np.stack([want[0], want[1][:, ::-1]]), name + ", the second image mirrored")
 
 
+def test_a_source_that_ends_off_a_16_byte_run_is_staged_byte_by_byte_at_its_end():
+    """One image of 5 x 7 pixels is 105 bytes: the last box row's segment ends at the allocation's last byte, so its second 16-byte run
+    crosses the end and is filled byte by byte (every other source here is a whole number of runs)."""
+    src = np.random.default_rng(SEED + 5).integers(0, 256, (1, 5, 7, 3), dtype=np.uint8)
+    rows = [(5, 7, 0, 0, 5, 7) + T + (0,)]
+    assert src.nbytes == 105 and src.nbytes % 16 != 0 and (4 * 7 * 3) // 16 * 16 + 32 > src.nbytes
+    want = W.resample_batch(src, rows)
+    _same_bytes(_resample(src, rows), want, "5 x 7")
+    _same_bytes(_resample(src, _mirrored(rows)), want[:, :, ::-1], "5 x 7, mirrored")
+
+
 def test_the_strips_take_74_taps_and_the_window_skips_rows():
     lo, cnt, _ = W.coeffs(4096, 224, np.arange(224))
     assert int(cnt.max()) == 74

@@ -147,18 +147,33 @@ def test_header_binding_and_both_libraries_have_the_entries():
         assert L.dyt_resample_scratch_bytes(128) == 128 * 23296      # the 11-tap route's scratch is what it was
 
 
-def test_python_refuses_by_name_when_the_library_lacks_the_entries():
+def _refuses_without(monkeypatch, _lib, symbol, call, named=None):
+    """``call`` raises a DyTError naming ``symbol`` (or ``named``) and "rebuild it" when the loaded library is one that lacks ``symbol``."""
+    real = _lib.lib()
+    stand_in = types.SimpleNamespace(**{n: getattr(real, n) for n in _lib.SYMBOLS if n != symbol and hasattr(real, n)})
+    monkeypatch.setattr(_lib, "lib", lambda fp16=False: stand_in)
+    with pytest.raises(_lib.DyTError) as e:
+        call()
+    assert (named or symbol) in str(e.value) and "rebuild it" in str(e.value), str(e.value)
+
+
+def test_python_refuses_by_name_when_the_library_lacks_the_entries(monkeypatch):
     import _lib
     import runtime
-    for fn in (_lib.resample_wide_u8, _lib.resample_wide_coeffs, runtime.DyTEngine.resample):
-        src = inspect.getsource(fn)
-        assert "dyt_resample_wide" in src and "hasattr(" in src and "rebuild it" in src
+    src = inspect.getsource(runtime.DyTEngine.resample)
+    assert "dyt_resample_wide" in src and "hasattr(" in src and "rebuild it" in src
+    # the wrappers delegate to one body: called with a library that lacks the symbol, before any argument is looked at
+    _refuses_without(monkeypatch, _lib, "dyt_resample_wide_u8", lambda: _lib.resample_wide_u8(None, None))
+    _refuses_without(monkeypatch, _lib, "dyt_resample_wide_scratch_bytes", lambda: _lib.resample_wide_u8(None, None), named="dyt_resample_wide_u8")
+    _refuses_without(monkeypatch, _lib, "dyt_resample_wide_coeffs", lambda: _lib.resample_wide_coeffs(None, 0, 64, 64))
 
 
 def test_resample_wide_h_is_hip_free_and_a_new_file_beside_the_old():
     src = open(os.path.join(CSRC, "resample_wide.h")).read()
     assert re.findall(r"#include\s*[<\"]([^>\"]+)", src) == ["resample.h"]      # readable by a host compiler alone, as that file is
-    assert src.count("#pragma clang fp contract(off)") == 1                      # the coefficient function; the filter is resample.h's
+    # the coefficient arithmetic and its pragma are resample.h's one template: no floating-point arithmetic of this file's own
+    assert "contract" not in src and not re.search(r"\b(float|double)\b", src)
+    assert open(os.path.join(CSRC, "resample.h")).read().count("#pragma clang fp contract(off)") == 2
     consts = dict(re.findall(r"\b(RSW_[A-Z_]+) = (\d+)", src))
     import _lib
     assert int(consts["RSW_KMAX"]) == W.KMAX == _lib.RESAMPLE_WIDE_KMAX == 75 and _lib.RESAMPLE_WIDE_COEFF_WORDS * 4 == PER_IMAGE
@@ -167,6 +182,10 @@ def test_resample_wide_h_is_hip_free_and_a_new_file_beside_the_old():
     assert re.search(r"^SRCS\s*=.*\bresample\.hip\b.*\bresample_wide\.hip\b", mk, re.M) and "contract" not in mk
     hip = open(os.path.join(CSRC, "resample_wide.hip")).read()
     assert "atomic" not in hip.replace("no atomics", "") and not re.search(r"\b(float|double)\b", hip.split("resample_wide_h_kernel(", 1)[1])
+    dev = open(os.path.join(CSRC, "resample_dev.h")).read()                      # the pixel helpers both vertical passes and the staging share
+    pixel = dev.split("namespace dyt {", 1)[1].split("the coefficient kernel of a bicubic route", 1)[0]
+    assert "resample_acc_pack" in pixel and "resample_stage_row" in pixel and '#include "resample_dev.h"' in hip
+    assert "atomic" not in dev.replace("No atomics", "") and not re.search(r"\b(float|double)\b", pixel)
 
 
 # ---- 2. csrc/resample_wide.h through the host compiler --------------------------------------------------------------------------------------
